@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark: Msamples/s of the MI355X sample loop on BASELINE.json's headline config.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f32|f64] [--config C]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--precision f32|f64] [--config C] [--full]
+                  [--dump-outputs DIR]
 
 One step = one full frame of config C (1920x1080, 500 spheres, 512 spp, 50 bounces): every rank
 renders its row-interleaved shard (rows r, r+N, ...) with the HIP megakernel, then rank 0 gathers
@@ -10,9 +11,18 @@ fixed as N grows -> "scaling": "strong").  With RCCL the shards are double-buffe
 is issued asynchronously and runs on RCCL's stream under frame k+1's render; frame k is assembled once
 its gather is done (--no-overlap: gather, then render the next frame).  The last frame's gather and
 assembly are inside the timed region.  Inputs (scene SoA, camera) are resident in HBM before
-the timed region.  Rank 0 prints one JSON line.  After the headline leg the same steps run in the
-other precision (fp64 = the reference's arithmetic when the headline is fp32), timed the same way,
-under the line's "f64" / "f32" key.
+the timed region.  Rank 0 prints one JSON line.  A plain run stops there: set-up, warm-up, the timed
+steps, the line.  --full adds what the headline figure does not need: after the headline leg the same
+steps run in the other precision (fp64 = the reference's arithmetic when the headline is fp32), timed
+the same way, under the line's "f64" / "f32" key (--other-precision 0 skips it), and the CPU baseline
+below (--cpu-seconds 0 skips it); without --full the line has no "f64" / "f32" key and its
+cpu_baseline is null.
+--dump-outputs DIR: after the headline leg's timed steps rank 0 writes the frame its last step left in
+  the caller's image buffer as DIR/image.npy (H x W x 3, the RGB8 values as float32).  A frame of more
+  than 64 MB in float32 is written as a fixed, seeded sample of its pixels instead: image.npy holds
+  their RGB rows (n x 3) and image_index.npy their flat pixel indices (y * W + x, float64).  Scene,
+  camera and RNG seed are functions of the arguments alone, so two runs with the same arguments dump
+  the same bytes.
 
 roofline: the trace kernel is bound by VALU issue (no MFMA; HBM is not binding).
   executed FLOP per launch = 64 lanes x the FLOP per lane of every wave-level cull and exact test the
@@ -35,7 +45,7 @@ roofline: the trace kernel is bound by VALU issue (no MFMA; HBM 
 --schedule dynamic: instead of one static row shard per rank, the ranks pull chunks (rows j, j+M, ...)
   from a counter in the process group's store, the reference's shared tile channel; every rank writes
   its chunks into a zeroed full frame and one RCCL reduce (sum) assembles the image on rank 0.
-cpu_baseline: the CPU restatement (oracle/, f64, 4-lane packets like PackedRays<4>), built
+cpu_baseline (--full): the CPU restatement (oracle/, f64, 4-lane packets like PackedRays<4>), built
   -march=native on this host, on every core this process may use (affinity, capped by the cgroup's
   CPU quota), over a bounded strided pixel sample of the same workload; cpu_baseline.packed: the
   reference-shaped run of the same path (explicit AVX2 packets, 128x128 tiles through a shared queue)
@@ -64,9 +74,14 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C")
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
-    ap.add_argument("--other-precision", type=int, default=1, help="also time the other precision (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other precision and the CPU baseline (a plain run does neither)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame of the headline leg to DIR/image.npy (float32)")
+    ap.add_argument("--other-precision", type=int, default=1,
+                    help="--full: also time the other precision (0 = skip)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0001)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline time budget (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may use")
     ap.add_argument("--pmc", default=os.path.join(REPO, "profiles", "pmc.json"))
     ap.add_argument("--max-spheres", type=int, default=0, help="experiment: truncate the scene (not a bench line)")
@@ -224,6 +239,24 @@ def cpu_baseline(flat, cam, depth, spp, seed, budget_s, threads, host):
                        "sample": "all 90000 pixels x 16 spp, 8 bounces, 3-sphere scene, f64 (best of 3)",
                        "ray_segments_per_sample": sa / (400 * 225 * 16)}
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: everything written stays under this
+DUMP_SAMPLE_PIXELS = 1 << 20   # pixels kept of a frame that is larger (12 MB of RGB + 8 MB of indices)
+
+
+def dump_outputs(out_dir, image):
+    """--dump-outputs: the assembled frame (H x W x 3 RGB8) as float32 .npy files under out_dir; a frame over
+    DUMP_MAX_BYTES in float32 as a fixed, seeded pixel sample with its indices."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    h, w, _ = image.shape
+    if image.size * 4 <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), image.astype(np.float32))
+        return
+    idx = np.sort(np.random.default_rng(0x5EED0001).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "image.npy"), image.reshape(h * w, 3)[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "image_index.npy"), idx.astype(np.float64))
 
 
 def main():
@@ -505,7 +538,9 @@ def main():
     if rank == 0 and os.environ.get("RT_BENCH_SAVE"):   # the headline precision's frame
         np.save(os.environ["RT_BENCH_SAVE"], image.cpu().numpy())
     other = None
-    if args.other_precision:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, image.cpu().numpy())
+    if args.full and args.other_precision:
         op = "f64" if args.precision == "f32" else "f32"
         other = (op, summarize(op, *leg(op)))
 
@@ -572,7 +607,7 @@ def main():
         }
         line["build"] = {"library": vinfo["version"], "source_hash": src_hash,
                          "library_matches_source": vinfo["src_hash"] == src_hash}
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             threads, host = cpu_share()
             threads = args.cpu_threads or threads
             line["cpu_baseline"] = cpu_baseline(flat, cam, depth, spp, args.seed, args.cpu_seconds, threads, host)

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(REPO, "bench.py")
 
@@ -41,6 +44,80 @@ def test_world_size_mismatch_exits_nonzero():
                                 MASTER_PORT="29517"), timeout=120)
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run times the headline leg only; the other precision and the CPU baseline need --full."""
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "d" and a.other_precision == 1 and a.cpu_seconds > 0
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the size limit is written whole as float32; a larger one as a fixed
+    pixel sample with its indices, the same from call to call and under the limit."""
+    b = _bench_module()
+    rng = np.random.default_rng(1)
+    img = rng.integers(0, 256, (9, 7, 3), dtype=np.uint8)
+    b.dump_outputs(str(tmp_path / "a"), img)
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    assert os.listdir(tmp_path / "a") == ["image.npy"]
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 9 * 7 * 3 * 4 - 1)   # one byte too small for the frame
+    monkeypatch.setattr(b, "DUMP_SAMPLE_PIXELS", 10)
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), img)
+    s, i = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "b" / "image_index.npy")
+    assert s.dtype == np.float32 and s.shape == (10, 3) and i.dtype == np.float64 and i.shape == (10,)
+    assert len(set(i.tolist())) == 10 and np.array_equal(s, img.reshape(-1, 3)[i.astype(np.int64)])
+    assert np.array_equal(s, np.load(tmp_path / "c" / "image.npy")) and np.array_equal(i, np.load(tmp_path / "c" / "image_index.npy"))
+    assert b.DUMP_SAMPLE_PIXELS * (3 * 4 + 8) <= b.DUMP_MAX_BYTES
+
+
+def _run_bench(*argv):
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", *argv], capture_output=True, text=True,
+                       env={k: v for k, v in _env().items() if k != "RT_BENCH_BACKEND"}, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_one_leg_and_dumps_its_frame(tmp_path):
+    """A plain run on config A (fp32): exactly --steps timed steps, no other-precision leg, no CPU baseline;
+    --dump-outputs writes the frame of the last timed step, which equals the oracle's fp32 golden frame."""
+    out = tmp_path / "dump"
+    line = _run_bench("--config", "A", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out))
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32" and line["unit"] == "Msamples/s"
+    assert "f64" not in line and "f32" not in line and line["cpu_baseline"] is None
+    assert line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    # value and ms_per_step are the same measurement, each rounded to 3 decimals (0.0005 ms on the latter)
+    assert line["value"] == pytest.approx(400 * 225 * 16 / (line["ms_per_step"] * 1e-3) / 1e6,
+                                          rel=0.0006 / line["ms_per_step"] + 1e-4)
+    assert line["dist"]["per_rank"][0]["pixels"] == 400 * 225
+    want = np.load(os.path.join(REPO, "tests", "golden", "config_a_f32.npz"))
+    assert int(want["seed"]) == 0x5EED0001 and (int(want["spp"]), int(want["max_bounces"])) == (16, 8)
+    got = np.load(out / "image.npy")
+    assert got.dtype == np.float32 and os.listdir(out) == ["image.npy"]
+    np.testing.assert_array_equal(got, want["rgb8"])
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_other_precision(tmp_path):
+    """--full on config A (fp64 headline): the fp32 leg is timed after it under the line's "f32" key, and
+    the dumped frame is still the headline leg's (the oracle's fp64 golden frame)."""
+    out = tmp_path / "dump"
+    line = _run_bench("--config", "A", "--precision", "f64", "--steps", "2", "--warmup", "1", "--full",
+                      "--cpu-seconds", "0", "--dump-outputs", str(out))
+    assert line["dtype"] == "f64" and line["f32"]["value"] > 0 and line["f32"]["ms_per_step"] > 0
+    assert "f64" not in line and line["cpu_baseline"] is None
+    want = np.load(os.path.join(REPO, "tests", "golden", "config_a.npz"))
+    np.testing.assert_array_equal(np.load(out / "image.npy"), want["rgb8"])
 
 
 def test_pmc_record_from_other_sources_is_stale():
