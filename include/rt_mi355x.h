@@ -122,6 +122,9 @@ typedef struct rt_stats {
 #define RT_KERNEL_MODE(id) (((id) >> 5) & 3u)    /* 0 live path, 1 vectorized, 2 scalar, 3 vectorized3 */
 #define RT_KERNEL_CAMQ(id) (((id) >> 7) & 1u)    /* pinhole camera batches */
 #define RT_KERNEL_MEGA(id) (((id) >> 8) & 1u)    /* four-level sweep (mega boxes; scenes of > 8 super groups) */
+/* Set: the sample-parallel kernels ran, trace_paths_split<T, W, CAMQ, MEGA> followed by finish_records<T>
+ * (rt_render_split_async); ROOT2 and MODE are 0 there. */
+#define RT_KERNEL_SPLIT(id) (((id) >> 9) & 1u)
 
 /* ---- flags ---- */
 #define RT_FLAG_F32 0x1u     /* compute in fp32 (default: fp64, the reference's arithmetic) */
@@ -184,6 +187,35 @@ int rt_context_set_scene(rt_context* ctx, const rt_scene* scene);
 int rt_render_async(rt_context* ctx, const rt_camera* camera, uint32_t max_bounces, uint32_t spp,
                     uint64_t seed, uint32_t flags, const rt_tile_range* range, void* d_rgb8,
                     void* d_linear, void* stream);
+/* rt_render_async with a pixel's samples dealt to several waves, for launches with fewer pixels than the
+ * chip has resident waves (previews, crops, thin shards, one pixel at a very high spp).  A work item is a
+ * (pixel, sample sub-range); a tracing kernel writes every sample's record into a context-owned record
+ * buffer and a second kernel, enqueued right behind it on `stream`, reduces each pixel in the reference's
+ * order.  The image is bit-identical to rt_render_async's.
+ * samples_per_item:
+ *   0  = the library plans from the launch shape (rt_split_plan).  When the plan is one item per pixel, or
+ *        the record buffer would exceed the scratch budget (24 GB), the call IS rt_render_async (same
+ *        kernel, same stats).
+ *   >0 = forced, any value in 1..2^20 (larger: RT_ERR_INVALID); a value >= spp runs one item per pixel
+ *        through the split kernels.
+ * Flags: RT_FLAG_F32 only.  RT_FLAG_ROOT2 or any RT_FLAG_MODE_* is RT_ERR_UNSUPPORTED; otherwise the
+ * argument checks are rt_render_async's.  More than 0x7FFFFFFF work items, or (forced) a record buffer over
+ * the scratch budget, is RT_ERR_UNSUPPORTED.
+ * rt_context_collect after it: RT_KERNEL_SPLIT(kernel_id) is set when the split kernels ran, kernel_ms
+ * covers both kernels, and samples, pixels, ray_segments and bounce_iters equal the unsplit render's.
+ * lane_slots, direct_sky_samples (0 here: sky pixels are traced like any other) and the executed-work
+ * counters may differ. */
+int rt_render_split_async(rt_context* ctx, const rt_camera* camera, uint32_t max_bounces, uint32_t spp,
+                          uint64_t seed, uint32_t flags, const rt_tile_range* range, void* d_rgb8,
+                          void* d_linear, void* stream, uint32_t samples_per_item);
+/* The plan rt_render_split_async makes for samples_per_item = 0; host only, needs no GPU.
+ * resident_waves: the waves the split kernels keep resident (CUs x 4 SIMDs x 5 waves in fp32, x 4 in fp64).
+ * Returns the samples per item (a multiple of 128, or spp when the plan is one item per pixel) and the
+ * item count.  The plan aims at about 8 items per resident wave and splits only launches with fewer pixels
+ * than resident waves.  RT_ERR_INVALID: NULL output, no pixels or spp == 0; RT_ERR_UNSUPPORTED: spp > 2^20 or more
+ * than 0x7FFFFFFF items. */
+int rt_split_plan(uint64_t n_pixels, uint32_t spp, uint32_t resident_waves, uint32_t* samples_per_item,
+                  uint64_t* n_items);
 /* RenderStat (renderer.rs:11-34) for the renders since the last call.
  * Synchronise `stream` (NULL = null stream), then report and reset the counters accumulated by the renders
  * enqueued since the last call (ray_segments, work counters, error flag).  kernel_ms = device time

@@ -132,6 +132,17 @@ template <typename T> struct KParams {
     uint32_t n_top, n_xg, n_xs;   // n_xs: always-exact spheres (the rest of their last group are dummies)
 };
 
+// Arguments of the sample-parallel kernels (trace_paths_split, finish_records): KParams first, so
+// cold_args<T>() reads it from the same kernarg offsets, then what only they need.  n_items counts
+// (pixel, sample sub-range) items there: item i is pixel i / nsub, samples [j S, min(spp, (j + 1) S)),
+// j = i % nsub.  scratch / scratch_stride: finish_records' per-wave position maps.
+template <typename T> struct SParams {
+    KParams<T> k;
+    char* rec;                 // record buffer: pixel x's region at x * k.sbytes (PScratch's y, c, e formats)
+    uint32_t S, nsub;          // samples per item, items per pixel
+    uint32_t n_pix;            // pixels of the rendered set (k.n_items / nsub)
+};
+
 constexpr int kSegShards = 256;
 constexpr uint32_t kFlagPinholeInternal = 0x80000000u;   // set by the host: defocus vectors are +-0
 constexpr int kWavesF32 = 6;   // default min-waves-per-SIMD targets (measured sweep);
@@ -189,6 +200,12 @@ template <typename T> using cptr = const __attribute__((address_space(4))) T*;
 // keeps ~40 camera SGPRs live across the whole persistent loop (SGPR spills into VGPR lanes).
 template <typename T> __device__ __forceinline__ cptr<KParams<T>> cold_args() {
     cptr<KParams<T>> k = (cptr<KParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+// The sample-parallel kernels' whole argument struct, read the same way.
+template <typename T> __device__ __forceinline__ cptr<SParams<T>> cold_split_args() {
+    cptr<SParams<T>> k = (cptr<SParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));
     return k;
 }

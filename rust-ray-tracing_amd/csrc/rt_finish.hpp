@@ -92,6 +92,49 @@ template <typename T> __device__ __forceinline__ PScratch<T> wave_scratch(uint32
     return PScratch<T>{q.scratch + (size_t)gw * q.scratch_stride, q.P, q.vbytes, q.sbytes, q.swide};
 }
 
+// Record view of the sample-parallel path (trace_paths_split writes, finish_records reads): the records
+// live in a launch-wide buffer, one region of sbytes per pixel of the rendered set in PScratch's y / c / e
+// formats, indexed by the absolute sample id.  The `s` every accessor takes is the pixel's index in the
+// set (not a wave's slot) and the region's offset is formed in 64 bits.  base: the position map of the
+// wave that reduces the pixel (finish_records; the trace kernels never touch it).
+template <typename T> struct RScratch {
+    char* base;        // wave-uniform
+    char* rec;
+    uint32_t P, sbytes, wide;
+    __device__ __forceinline__ uint32_t map(uint32_t q) const {
+        if (wide & 2u) return *(const uint32_t*)(base + 4u * q);
+        return PScratch<T>::from16(*(const uint16_t*)(base + 2u * q));
+    }
+    __device__ __forceinline__ void set_map(uint32_t q, uint32_t smp) const {
+        if (wide & 2u) *(uint32_t*)(base + 4u * q) = smp;
+        else *(uint16_t*)(base + 2u * q) = PScratch<T>::to16(smp);
+    }
+    __device__ __forceinline__ char* region(uint32_t s) const { return rec + (size_t)s * (size_t)sbytes; }
+    __device__ __forceinline__ T& y(uint32_t s, uint32_t i) const { return *(T*)(region(s) + i * (uint32_t)sizeof(T)); }
+    __device__ __forceinline__ C3<T>& c(uint32_t s, uint32_t i) const {
+        return *(C3<T>*)(region(s) + (P + 3u * i) * (uint32_t)sizeof(T));
+    }
+    __device__ __forceinline__ void store_c(uint32_t s, uint32_t i, T x, T y, T z) const {
+        T* r = &c(s, i).x;
+        r[0] = x; r[1] = y; r[2] = z;
+    }
+    __device__ __forceinline__ uint32_t e(uint32_t s, uint32_t i) const {
+        const char* b = region(s) + 4u * P * (uint32_t)sizeof(T);
+        return (wide & 1u) ? *(const uint32_t*)(b + 4u * i) : (uint32_t) * (const uint8_t*)(b + i);
+    }
+    __device__ __forceinline__ void set_e(uint32_t s, uint32_t i, uint32_t v) const {
+        char* b = region(s) + 4u * P * (uint32_t)sizeof(T);
+        if (wide & 1u) *(uint32_t*)(b + 4u * i) = v;
+        else *(uint8_t*)(b + i) = (uint8_t)v;
+    }
+};
+
+// The launch's record view, from the sample-parallel kernels' arguments (no map: the trace kernels write
+// records only).
+template <typename T> __device__ __forceinline__ RScratch<T> split_records() {
+    const auto& q = *cold_split_args<T>();
+    return RScratch<T>{nullptr, q.rec, q.k.P, q.k.sbytes, q.k.swide};
+}
 
 // PScratch sizes: the map (u16, u32 past 32764 positions), the records (e u8, u32 when depth > 254).
 __host__ __device__ inline uint32_t paths_wide(uint32_t P, uint32_t depth) { return (depth > 254u ? 1u : 0u) | (P > 32764u ? 2u : 0u); }
@@ -162,8 +205,8 @@ __device__ __forceinline__ T reduce_positions(uint32_t P, uint32_t* hist, T (*st
 // staged and summed one after the other, so a 512-position pixel waits for 4 load round trips, not 8
 // (round 5, same-box C fp32 +0.4 %, fp64 +0.6 %, E +0.6 %; prefetching the next pair's map entries as well
 // lost, profiles/r05/reduce_pair_ab.txt).
-template <typename T, typename G>
-__device__ __forceinline__ T reduce_live16(const PScratch<T>& sc, uint32_t s, uint32_t spp, uint32_t P, const uint16_t* lmap,
+template <typename T, typename SC, typename G>
+__device__ __forceinline__ T reduce_live16(const SC& sc, uint32_t s, uint32_t spp, uint32_t P, const uint16_t* lmap,
                                            bool lm, uint32_t* hist, T (*stage)[64], G&& generic) {
     const uint32_t lane = threadIdx.x & 63u;
     T* accl = (T*)hist;
@@ -292,8 +335,9 @@ __device__ __forceinline__ void finish_sky_direct(uint32_t item, uint32_t col, u
 // The position map in LDS (live-path kernels without the mega level, P <= kLMapCap positions: config C's
 // 512 spp): the replay's scattered u16 writes, the map's initialisation and the reduction's reads stay
 // on the CU instead of going to HBM as partial lines.  Larger P uses the global map in PScratch.
-template <typename T, int MODE, bool BALLOT01 = true>
-__device__ __forceinline__ uint32_t finish_pixel(const PScratch<T>& sc, uint32_t s, uint32_t item, uint32_t* hist,
+// SC: the record view, a wave's PScratch (s: its slot) or the sample-parallel path's RScratch (s: the pixel).
+template <typename T, int MODE, bool BALLOT01 = true, typename SC = PScratch<T>>
+__device__ __forceinline__ uint32_t finish_pixel(const SC& sc, uint32_t s, uint32_t item, uint32_t* hist,
                                                  T (*stage)[64], uint16_t* lmap, bool all_e0 = false) {
     const auto& q = *cold_args<T>();
     const uint32_t lane = threadIdx.x & 63u;

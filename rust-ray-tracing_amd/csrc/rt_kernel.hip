@@ -29,10 +29,12 @@
 //
 // Source layout (one translation unit): rt_experiments.hpp (build kinds), rt_common.hpp (layouts,
 // kernel arguments, scalar-load pipelines), rt_sweep.hpp (general sweep), rt_camera.hpp (primary
-// rays, scatter), rt_finish.hpp (replay + reduction), rt_trace.hpp (the persistent kernel),
-// rt_layout.hpp (host-side scene layout); this file holds the C ABI.
+// rays, scatter), rt_finish.hpp (replay + reduction), rt_trace.hpp + rt_trace_body.hpp (the persistent kernel),
+// rt_layout.hpp (host-side scene layout), rt_split_plan.hpp (the sample-parallel plan, host only); this
+// file holds the C ABI.
 #include "rt_trace.hpp"
 #include "rt_layout.hpp"
+#include "rt_split_plan.hpp"
 
 #include <chrono>
 #include <mutex>
@@ -95,6 +97,8 @@ struct rt_context {
     uint32_t* counter = nullptr;   // persistent-kernel claim-stream counters (zeroed before each launch)
     void* scratch = nullptr;       // per-wave ray state (grown on demand)
     size_t scratch_bytes = 0;
+    void* records = nullptr;       // the sample-parallel path's record buffer (grown on demand)
+    size_t records_bytes = 0;
     int n_cu = 0;
     uint64_t samples = 0, pixels = 0;
     hipStream_t last_stream = nullptr;   // stream of the previous render (they share scratch and tables)
@@ -209,6 +213,7 @@ extern "C" int rt_context_destroy(rt_context* c) {
     (void)hipStreamSynchronize(c->stream);
     free_scene(c);
     (void)hipFree(c->segs); (void)hipFree(c->err); (void)hipFree(c->counter); (void)hipFree(c->scratch);
+    (void)hipFree(c->records);
     (void)hipEventDestroy(c->ev_first); (void)hipEventDestroy(c->ev_last);
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -409,6 +414,7 @@ static bool check_range(const rt_camera* cam, const rt_tile_range* r) {
 }
 
 static int ensure_scratch(rt_context* c, size_t bytes, hipStream_t st);
+static int ensure_records(rt_context* c, size_t bytes, hipStream_t st);
 
 // The kernel instantiation for (flags, waves-per-SIMD target, camera batches, mega level).  W < 0:
 // the defaults (RT_WAVES unset).  The mega level (scenes with more than 8 super groups) has its own
@@ -456,9 +462,31 @@ static KernelPick<T> pick_kernel(uint32_t flags, int W, bool mega, bool big) {
     }
 }
 
+// The sample-parallel kernels (rt_render_split_async): trace_paths_split<T, W, CAMQ, MEGA> at one occupancy
+// per precision, the one small launches take today (fp32 5 waves per SIMD, fp64 4), and finish_records<T>.
+template <typename T> constexpr int kWavesSplit = sizeof(T) == 4 ? 5 : 4;
+template <typename T> struct SplitPick {
+    void (*fn)(SParams<T>);
+    uint32_t id;
+    int W;
+};
+template <typename T, bool CAMQ>
+static SplitPick<T> pick_split(bool mega) {
+    constexpr int W = kWavesSplit<T>;
+    const uint32_t id = 0x8000u | (sizeof(T) == 8 ? 1u : 0u) | ((uint32_t)W << 1) | (CAMQ ? 1u << 7 : 0u) |
+                        (mega ? 1u << 8 : 0u) | (1u << 9);
+    return SplitPick<T>{mega ? trace_paths_split<T, W, CAMQ, true> : trace_paths_split<T, W, CAMQ, false>, id, W};
+}
+// A render's split: S samples per work item, nsub items per pixel (rt_split_plan.hpp).
+struct SplitShape { uint32_t S, nsub; };
+constexpr uint64_t kScratchBudget = 24ull << 30;   // scratch (and record buffer) bytes a launch may ask for
+
+// split: the sample-parallel path (trace_paths_split over (pixel, sample sub-range) items, then
+// finish_records); nullptr: trace_paths.
 template <typename T>
 static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_t spp, uint64_t seed, uint32_t flags,
-                    const rt_tile_range& rg, void* d_rgb, void* d_lin, hipStream_t st) {
+                    const rt_tile_range& rg, void* d_rgb, void* d_lin, hipStream_t st,
+                    const SplitShape* split = nullptr) {
     KParams<T> p;
     memset(&p, 0, sizeof(p));
     const bool f64 = sizeof(T) == 8;
@@ -552,6 +580,8 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
     p.err = c->err;
     p.counter = c->counter;
     p.n_items = rg.row_count * rg.col_count;
+    const uint32_t n_pix = p.n_items;
+    if (split) p.n_items = n_pix * split->nsub;   // <= 0x7FFFFFFF (rt_render_split_async)
 
     // Persistent grid: as many 4-wave workgroups as stay resident, never more waves than pixels.
     // Minimum waves per SIMD the register allocation targets.  RT_WAVES (4..7; read at every
@@ -565,6 +595,9 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
     const KernelPick<T> pick = camq ? pick_kernel<T, true>(flags, W, p.n_mg > 0, big)
                                     : pick_kernel<T, false>(flags, W, p.n_mg > 0, big);
     void (*kern)(KParams<T>) = pick.fn;
+    const SplitPick<T> spick = camq ? pick_split<T, true>(p.n_mg > 0) : pick_split<T, false>(p.n_mg > 0);
+    const void* const kfn = split ? (const void*)spick.fn : (const void*)kern;
+    const int kW = split ? spick.W : pick.W;
     if (camq) {
         p.camsph = (const T*)(f64 ? c->cam64 : c->cam32);
         p.camf = (const float*)(f64 ? c->camf64 : c->camf32);
@@ -596,7 +629,7 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
         }
     }
     int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, 256, 0));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, 0));
     if (per_cu < 1) per_cu = 1;
     // 4-wave workgroups: W waves per SIMD is W workgroups per CU.  Fewer means the kernel's LDS (or
     // registers) cut its occupancy below the target it was built for (kParkC takes fp32 W6 to 26.8 of the
@@ -604,21 +637,23 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
     // A/B build is ever measured at an occupancy other than the one it names (rt_stats reports both).
     c->last_kernel_id = 0;   // 0: no kernel (ids have bit 15 set)
     c->last_wg_per_cu = 0;
-    if (per_cu < pick.W)
+    if (per_cu < kW)
         return fail(RT_ERR_UNSUPPORTED, std::string(RT_BUILD_KIND) + " build: " + std::to_string(per_cu) +
-                                            " workgroups per CU resident, kernel built for " + std::to_string(pick.W) +
+                                            " workgroups per CU resident, kernel built for " + std::to_string(kW) +
                                             " (its LDS or registers grew past the occupancy target)");
-    c->last_kernel_id = pick.id;   // only a kernel that passed the check is ever reported
+    c->last_kernel_id = split ? spick.id : pick.id;   // only a kernel that passed the check is ever reported
     c->last_wg_per_cu = (uint32_t)per_cu;
     uint64_t nblocks = (uint64_t)c->n_cu * (uint64_t)per_cu;
     const uint64_t need = ((uint64_t)p.n_items + 3) / 4;
     if (nblocks > need) nblocks = need;
     {   // G: the largest power of two <= min(kMaxBlock, kBlockSamples / spp, pixels per wave / kBlockShare),
         // raised to kClaimSpp / spp (claim rate, below) where the share bound would go under it
+        // (the sample-parallel path: an item's samples for spp, items for pixels)
+        const uint32_t ispp = split ? std::min(split->S, spp) : spp;
         const uint64_t per_wave = (uint64_t)p.n_items / (4u * nblocks);
-        const uint64_t g = std::max<uint64_t>({1u, std::min<uint64_t>({(uint64_t)kMaxBlock, kBlockSamples / spp,
+        const uint64_t g = std::max<uint64_t>({1u, std::min<uint64_t>({(uint64_t)kMaxBlock, kBlockSamples / ispp,
                                                                        per_wave / kBlockShare}),
-                                               std::min<uint64_t>((uint64_t)kMaxBlock, (kClaimSpp + spp - 1) / spp)});
+                                               std::min<uint64_t>((uint64_t)kMaxBlock, (kClaimSpp + ispp - 1) / ispp)});
         uint32_t G = 1;
         while (2u * G <= g) G *= 2u;
         // diagnostics (tools/waves_ab.py --block): RT_BLOCK_G overrides the largest block (1..16, a power of two)
@@ -629,9 +664,32 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
     p.swide = paths_wide(p.P, depth);
     p.vbytes = paths_vbytes(p.P, p.swide, (flags & RT_FLAG_MODE_VECTORIZED3) != 0u);
     p.sbytes = paths_sbytes(p.P, sizeof(T), p.swide);
+    if (split) {
+        // The trace kernel writes the record buffer (one region per pixel) and needs no scratch; the finish
+        // kernel's waves stride over the pixels, each with a position map of its own in the scratch.
+        p.scratch_stride = (size_t)p.vbytes;
+        uint64_t fblocks = std::min<uint64_t>(((uint64_t)n_pix + 3) / 4, (uint64_t)c->n_cu * 8u);
+        fblocks = std::max<uint64_t>(1u, std::min<uint64_t>(fblocks, kScratchBudget / (4 * p.scratch_stride)));
+        int rc = ensure_records(c, (size_t)n_pix * p.sbytes, st);
+        if (rc == RT_OK) rc = ensure_scratch(c, p.scratch_stride * fblocks * 4, st);
+        if (rc != RT_OK) return rc;
+        p.scratch = (char*)c->scratch;
+        SParams<T> sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.k = p;
+        sp.rec = (char*)c->records;
+        sp.S = split->S;
+        sp.nsub = split->nsub;
+        sp.n_pix = n_pix;
+        HIPCHK(hipMemsetAsync(c->counter, 0, kStreams * kCtrStride * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(spick.fn, dim3((uint32_t)nblocks), dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(finish_records<T>, dim3((uint32_t)fblocks), dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        return RT_OK;
+    }
     p.scratch_stride = (size_t)p.vbytes + (size_t)kSlots * p.sbytes;
     // Keep the scratch within a fixed budget: fewer resident waves for very large spp.
-    const uint64_t kScratchBudget = 24ull << 30;
     const uint64_t max_blocks = kScratchBudget / (4 * p.scratch_stride);
     if (nblocks > max_blocks) nblocks = max_blocks > 0 ? max_blocks : 1;
     const int rc = ensure_scratch(c, p.scratch_stride * nblocks * 4, st);
@@ -655,25 +713,67 @@ static int ensure_scratch(rt_context* c, size_t bytes, hipStream_t st) {
     return RT_OK;
 }
 
-extern "C" int rt_render_async(rt_context* c, const rt_camera* cam, uint32_t max_bounces, uint32_t spp, uint64_t seed,
-                               uint32_t flags, const rt_tile_range* range, void* d_rgb8, void* d_linear, void* stream) {
-    if (!c || !cam) return fail(RT_ERR_INVALID, "rt_render_async: NULL argument");
-    if (spp == 0) return fail(RT_ERR_INVALID, "rt_render_async: spp == 0 (the reference panics: 0/0 in to_u8_array)");
-    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, "rt_render_async: unknown flag bits");
+static int ensure_records(rt_context* c, size_t bytes, hipStream_t st) {
+    if (bytes <= c->records_bytes) return RT_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipDeviceSynchronize());
+    if (c->records) HIPCHK(hipFree(c->records));
+    c->records = nullptr;
+    c->records_bytes = 0;
+    HIPCHK(hipMalloc(&c->records, bytes));
+    c->records_bytes = bytes;
+    return RT_OK;
+}
+
+// rt_render_async (split_mode < 0) and rt_render_split_async (split_mode 0: the auto plan; 1: samples_per_item
+// forced).  who: the entry point's name, for the error messages.
+static int render_async(rt_context* c, const rt_camera* cam, uint32_t max_bounces, uint32_t spp, uint64_t seed,
+                        uint32_t flags, const rt_tile_range* range, void* d_rgb8, void* d_linear, void* stream,
+                        const char* who_, int split_mode, uint32_t samples_per_item) {
+    const std::string who = who_;
+    if (!c || !cam) return fail(RT_ERR_INVALID, who + ": NULL argument");
+    if (spp == 0) return fail(RT_ERR_INVALID, who + ": spp == 0 (the reference panics: 0/0 in to_u8_array)");
+    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
     {
         const uint32_t modes = flags & (RT_FLAG_MODE_VECTORIZED | RT_FLAG_MODE_SCALAR | RT_FLAG_MODE_VECTORIZED3);
         if (modes & (modes - 1u))
-            return fail(RT_ERR_INVALID, "rt_render_async: the RT_FLAG_MODE_* flags are exclusive");
+            return fail(RT_ERR_INVALID, who + ": the RT_FLAG_MODE_* flags are exclusive");
     }
-    if (spp > (1u << 20)) return fail(RT_ERR_UNSUPPORTED, "rt_render_async: spp > 2^20");
+    if (spp > (1u << 20)) return fail(RT_ERR_UNSUPPORTED, who + ": spp > 2^20");
     if ((flags & RT_FLAG_F32) && max_bounces > RT_MAX_BOUNCES_F32)   // rng<float>'s counter (rt_device.hpp)
-        return fail(RT_ERR_UNSUPPORTED, "rt_render_async: fp32 with max_bounces > RT_MAX_BOUNCES_F32 (3839)");
-    if (cam->image_width == 0 || cam->image_height == 0) return fail(RT_ERR_INVALID, "rt_render_async: empty image");
+        return fail(RT_ERR_UNSUPPORTED, who + ": fp32 with max_bounces > RT_MAX_BOUNCES_F32 (3839)");
+    if (cam->image_width == 0 || cam->image_height == 0) return fail(RT_ERR_INVALID, who + ": empty image");
     if ((uint64_t)cam->image_width * cam->image_height > 0xFFFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "image too large");
     rt_tile_range rg = range ? *range : rt_tile_range{0, 1, cam->image_height, 0, cam->image_width};
-    if (!check_range(cam, &rg)) return fail(RT_ERR_INVALID, "rt_render_async: tile range outside the image");
+    if (!check_range(cam, &rg)) return fail(RT_ERR_INVALID, who + ": tile range outside the image");
     if ((uint64_t)rg.row_count * rg.col_count > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "too many pixels in one call");
     const bool f32 = (flags & RT_FLAG_F32) != 0;
+    SplitShape shape{spp, 1u};
+    bool split = false;
+    if (split_mode >= 0) {
+        if (flags & ~RT_FLAG_F32) return fail(RT_ERR_UNSUPPORTED, who + ": the live path only (no RT_FLAG_ROOT2, no RT_FLAG_MODE_*)");
+        const uint64_t n_pix = (uint64_t)rg.row_count * rg.col_count;
+        const uint32_t P = 4u * ((spp + 3u) / 4u);
+        const uint64_t rec_bytes = n_pix * paths_sbytes(P, f32 ? 4u : 8u, paths_wide(P, max_bounces));
+        if (split_mode == 0) {
+            // resident waves of the split kernels: 4-wave workgroups at their occupancy target on every CU
+            const uint32_t waves = (uint32_t)c->n_cu * 4u * (uint32_t)(f32 ? kWavesSplit<float> : kWavesSplit<double>);
+            uint64_t n_items = 0;
+            const int prc = split_plan(n_pix, spp, waves, &shape.S, &n_items);
+            if (prc != kPlanOk) return fail(prc, who + ": no plan for this launch shape");
+            shape.nsub = split_nsub(spp, shape.S);
+            split = shape.nsub > 1u && rec_bytes <= kScratchBudget;   // else: this call is rt_render_async
+        } else {
+            if (samples_per_item == 0 || samples_per_item > (1u << 20))
+                return fail(RT_ERR_INVALID, who + ": samples_per_item outside 1..2^20");
+            shape.S = samples_per_item;
+            shape.nsub = split_nsub(spp, shape.S);
+            if (n_pix * shape.nsub > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many work items in one call");
+            if (rec_bytes > kScratchBudget) return fail(RT_ERR_UNSUPPORTED, who + ": record buffer over the scratch budget");
+            split = true;
+        }
+    }
+    const SplitShape* const sh = split ? &shape : nullptr;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the HIP null stream
     // Renders on one context share its work counter, scratch and camera table: a render on a new
@@ -685,12 +785,31 @@ extern "C" int rt_render_async(rt_context* c, const rt_camera* cam, uint32_t max
         HIPCHK(hipEventRecord(c->ev_first, st));
         c->have_first = true;
     }
-    const int rc = f32 ? launch_t<float>(c, cam, max_bounces, spp, seed, flags, rg, d_rgb8, d_linear, st)
-                       : launch_t<double>(c, cam, max_bounces, spp, seed, flags, rg, d_rgb8, d_linear, st);
+    const int rc = f32 ? launch_t<float>(c, cam, max_bounces, spp, seed, flags, rg, d_rgb8, d_linear, st, sh)
+                       : launch_t<double>(c, cam, max_bounces, spp, seed, flags, rg, d_rgb8, d_linear, st, sh);
     if (rc != RT_OK) return rc;
     HIPCHK(hipEventRecord(c->ev_last, st));
     c->pixels += (uint64_t)rg.row_count * rg.col_count;
     c->samples += (uint64_t)rg.row_count * rg.col_count * spp;
+    return RT_OK;
+}
+
+extern "C" int rt_render_async(rt_context* c, const rt_camera* cam, uint32_t max_bounces, uint32_t spp, uint64_t seed,
+                               uint32_t flags, const rt_tile_range* range, void* d_rgb8, void* d_linear, void* stream) {
+    return render_async(c, cam, max_bounces, spp, seed, flags, range, d_rgb8, d_linear, stream, "rt_render_async", -1, 0u);
+}
+
+extern "C" int rt_render_split_async(rt_context* c, const rt_camera* cam, uint32_t max_bounces, uint32_t spp,
+                                     uint64_t seed, uint32_t flags, const rt_tile_range* range, void* d_rgb8,
+                                     void* d_linear, void* stream, uint32_t samples_per_item) {
+    return render_async(c, cam, max_bounces, spp, seed, flags, range, d_rgb8, d_linear, stream, "rt_render_split_async",
+                        samples_per_item == 0u ? 0 : 1, samples_per_item);
+}
+
+extern "C" int rt_split_plan(uint64_t n_pixels, uint32_t spp, uint32_t resident_waves, uint32_t* samples_per_item,
+                             uint64_t* n_items) {
+    const int rc = split_plan(n_pixels, spp, resident_waves, samples_per_item, n_items);
+    if (rc != kPlanOk) return fail(rc, "rt_split_plan: no plan (NULL output, no pixels or samples, spp > 2^20 or too many items)");
     return RT_OK;
 }
 

@@ -2,10 +2,12 @@
 //
 //   rt-render [--scene scene.toml] [--width 3840] [--height 2160] [--spp 100] [--bounces 50]
 //             [--seed 0x5EED0001] [--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar]
-//             [--out output.png|.ppm] [--block-size B] [--dump-scene]
+//             [--out output.png|.ppm] [--block-size B] [--sample-parallel] [--dump-scene]
 //
 // --mode picks which of the reference's renderers is reproduced (include/rt_mi355x.h): the live
 // render_vectorized2 (default), render_vectorized, or the scalar render.
+// --sample-parallel deals each pixel's samples to several waves where a launch has fewer pixels than the chip
+// has waves (rt_render_split_async's own plan; small frames at a high spp; the live path only, same image).
 //
 // Defaults are main.rs's hard-coded values (scene.toml in the working directory, 3840x2160, 50
 // bounces, 100 spp, camera from (16,2,18.5) looking at the origin, vfov 30, focal 10, no defocus,
@@ -68,7 +70,7 @@ int main(int argc, char** argv) {
     std::string scene_path = "scene.toml", out = "output.png";
     uint32_t width = 3840, height = 2160, spp = 100, bounces = 50, flags = 0, block_size = 0;
     uint64_t seed = 0x5EED0001ull;
-    bool dump = false;
+    bool dump = false, sample_parallel = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -93,11 +95,12 @@ int main(int argc, char** argv) {
         }
         else if (a == "--out") out = next();
         else if (a == "--block-size") block_size = (uint32_t)std::stoul(next());
+        else if (a == "--sample-parallel") sample_parallel = true;
         else if (a == "--dump-scene") dump = true;
         else if (a == "-h" || a == "--help") {
             std::puts("rt-render [--scene scene.toml] [--width W] [--height H] [--spp S] [--bounces B] [--seed N] "
                       "[--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar] [--out output.png] [--block-size B] "
-                      "[--dump-scene]");
+                      "[--sample-parallel] [--dump-scene]");
             return 0;
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -124,7 +127,7 @@ int main(int argc, char** argv) {
         std::printf("\tViewport Top Left Corner: %s\n", rs3(camera.c.ulc).c_str());
         std::printf("\t Number of objects: \t %zu\n", scene.len());                           // main.rs:60
 
-        GpuRenderer renderer(seed, flags, block_size);   // block_size 128: TileRenderer::new(None, 128), main.rs:62
+        GpuRenderer renderer(seed, flags, block_size, sample_parallel);   // block_size 128: TileRenderer::new(None, 128), main.rs:62
         std::fprintf(stderr, "Rendering %u by %u image on %s (%s)...\n", width, height, rt_version(),
                      (flags & RT_FLAG_F32) ? "fp32" : "fp64");
         auto [image, stat] = renderer.render(bounces, spp, scene, camera);                     // main.rs:64

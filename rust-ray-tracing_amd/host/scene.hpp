@@ -277,11 +277,16 @@ struct Renderer {   // renderer.rs:38-40
 // context, and after each the reference's per-block line (renderer.rs:339), with the block's pixel
 // rate from the launch's kernel time: "Device 0 complete block (x, y) at R px/s".  The image is the
 // same either way (the RNG is keyed by the global pixel index).
+// sample_parallel: every launch goes through rt_render_split_async with its own plan, which deals a pixel's
+// samples to several waves where the launch has fewer pixels than the chip has waves (the live path only;
+// the same image).
 struct GpuRenderer : Renderer {
     uint64_t seed;
     uint32_t flags;
     uint32_t block_size;
-    explicit GpuRenderer(uint64_t s = 0x5EED0001ull, uint32_t f = 0, uint32_t b = 0) : seed(s), flags(f), block_size(b) {}
+    bool sample_parallel;
+    explicit GpuRenderer(uint64_t s = 0x5EED0001ull, uint32_t f = 0, uint32_t b = 0, bool sp = false)
+        : seed(s), flags(f), block_size(b), sample_parallel(sp) {}
     std::pair<RgbImage, RenderStat> render(size_t max_bounces, size_t spp, const Scene& scene,
                                            const Camera& camera) override {
         const auto t0 = std::chrono::steady_clock::now();
@@ -290,13 +295,15 @@ struct GpuRenderer : Renderer {
         RgbImage img{camera.image_width(), camera.image_height(), {}};
         img.data.resize((size_t)img.width * img.height * 3);
         rt_stats st{};
-        if (block_size == 0) {
+        if (block_size == 0 && sample_parallel) {   // one launch of the whole image on a device context
+            render_blocks(rs, camera, (uint32_t)max_bounces, (uint32_t)spp, img, st, std::max(img.width, img.height), false);
+        } else if (block_size == 0) {
             const int rc = rt_render(&rs, &camera.c, (uint32_t)max_bounces, (uint32_t)spp, seed, flags, nullptr,
                                      img.data.data(), nullptr, &st);
             if (rc == RT_ERR_RANGE) throw Panic(std::string("assertion failed: ") + rt_last_error());
             if (rc != RT_OK) throw Panic(std::string("rt_render failed: ") + rt_last_error());
         } else {
-            render_blocks(rs, camera, (uint32_t)max_bounces, (uint32_t)spp, img, st);
+            render_blocks(rs, camera, (uint32_t)max_bounces, (uint32_t)spp, img, st, block_size, true);
         }
         const size_t npx = (size_t)img.width * img.height;
         RenderStat stat(std::chrono::steady_clock::now() - t0, npx, st);
@@ -305,7 +312,7 @@ struct GpuRenderer : Renderer {
 
   private:
     void render_blocks(const rt_scene& rs, const Camera& camera, uint32_t max_bounces, uint32_t spp, RgbImage& img,
-                       rt_stats& total) {
+                       rt_stats& total, uint32_t B, bool print_blocks) {
         struct Ctx {
             rt_context* c = nullptr;
             void* buf = nullptr;
@@ -317,17 +324,22 @@ struct GpuRenderer : Renderer {
         };
         chk(rt_context_create(0, &x.c), "rt_context_create");
         chk(rt_context_set_scene(x.c, &rs), "rt_context_set_scene");
-        const uint32_t B = block_size, W = img.width, H = img.height;
-        chk(rt_device_alloc(x.c, (size_t)B * B * 3, &x.buf), "rt_device_alloc");
-        std::vector<uint8_t> tile((size_t)B * B * 3);
+        const uint32_t W = img.width, H = img.height;
+        const size_t tile_px = (size_t)std::min(B, W) * std::min(B, H);
+        chk(rt_device_alloc(x.c, tile_px * 3, &x.buf), "rt_device_alloc");
+        std::vector<uint8_t> tile(tile_px * 3);
         const uint32_t nbx = (W + B - 1) / B, nby = (H + B - 1) / B;   // renderer.rs:248-266
         bool range_err = false;
         for (uint32_t by = 0; by < nby; ++by)
             for (uint32_t bx = 0; bx < nbx; ++bx) {
                 const uint32_t c0 = bx * B, r0 = by * B;
                 const rt_tile_range tr{r0, 1, std::min(B, H - r0), c0, std::min(B, W - c0)};
-                chk(rt_render_async(x.c, &camera.c, max_bounces, spp, seed, flags, &tr, x.buf, nullptr, nullptr),
-                    "rt_render_async");
+                if (sample_parallel)
+                    chk(rt_render_split_async(x.c, &camera.c, max_bounces, spp, seed, flags, &tr, x.buf, nullptr, nullptr, 0u),
+                        "rt_render_split_async");
+                else
+                    chk(rt_render_async(x.c, &camera.c, max_bounces, spp, seed, flags, &tr, x.buf, nullptr, nullptr),
+                        "rt_render_async");
                 rt_stats st{};
                 const int rc = rt_context_collect(x.c, nullptr, &st);
                 if (rc == RT_ERR_RANGE) range_err = true;
@@ -338,7 +350,7 @@ struct GpuRenderer : Renderer {
                     std::memcpy(&img.data[((size_t)(r0 + r) * W + c0) * 3], &tile[(size_t)r * tr.col_count * 3],
                                 (size_t)tr.col_count * 3);
                 // renderer.rs:339: "Thread {} complete block ({}, {}) at {:.2} px/s"
-                std::printf("Device 0 complete block (%u, %u) at %.2f px/s\n", bx, by, st.pixels_per_second);
+                if (print_blocks) std::printf("Device 0 complete block (%u, %u) at %.2f px/s\n", bx, by, st.pixels_per_second);
                 total.kernel_ms += st.kernel_ms;
                 total.pixels += st.pixels;
                 total.samples += st.samples;

@@ -76,12 +76,18 @@ class RtStats(ctypes.Structure):
     ]
 
 
+def RT_KERNEL_SPLIT(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_SPLIT: the sample-parallel kernels ran (rt_render_split_async)."""
+    return (kernel_id >> 9) & 1
+
+
 def kernel_info(kernel_id):
     """rt_stats.kernel_id decoded (include/rt_mi355x.h RT_KERNEL_*): the trace_paths instantiation that ran."""
     if kernel_id == 0:
         return None
     return {"T": "double" if kernel_id & 1 else "float", "W": (kernel_id >> 1) & 7, "root2": bool((kernel_id >> 4) & 1),
-            "mode": (kernel_id >> 5) & 3, "camq": bool((kernel_id >> 7) & 1), "mega": bool((kernel_id >> 8) & 1)}
+            "mode": (kernel_id >> 5) & 3, "camq": bool((kernel_id >> 7) & 1), "mega": bool((kernel_id >> 8) & 1),
+            "split": bool(RT_KERNEL_SPLIT(kernel_id))}
 
 
 def kernel_name(kernel_id):
@@ -90,6 +96,8 @@ def kernel_name(kernel_id):
     if k is None:
         return None
     b = lambda v: "true" if v else "false"
+    if k["split"]:   # trace_paths_split<T,W,CAMQ,MEGA> (finish_records<T> follows it)
+        return f"trace_paths_split<{k['T']},{k['W']},{b(k['camq'])},{b(k['mega'])}>"
     return f"trace_paths<{k['T']},{k['W']},{b(k['root2'])},{k['mode']},{b(k['camq'])},{b(k['mega'])}>"
 
 
@@ -117,14 +125,14 @@ LIB_PATH = os.environ.get("RT_MI355X_LIB") or os.path.join(PKG_DIR, "lib", "libr
 EXPORTED = [
     "rt_camera_new", "rt_metal_clamp_fuzz", "rt_render", "rt_context_create", "rt_context_destroy",
     "rt_context_set_scene", "rt_render_async", "rt_context_collect", "rt_device_alloc", "rt_device_free",
-    "rt_memcpy_d2h", "rt_last_error", "rt_version",
+    "rt_memcpy_d2h", "rt_last_error", "rt_version", "rt_render_split_async", "rt_split_plan",
 ]
 
 _lib = None
 
 # The sources the Makefile hashes into rt_version() ("src=<hash>"), in its order (SRC, then HDR).
 KERNEL_SOURCES = ["rt_kernel.hip", "rt_experiments.hpp", "rt_common.hpp", "rt_sweep.hpp", "rt_camera.hpp",
-                  "rt_finish.hpp", "rt_trace.hpp", "rt_layout.hpp", "rt_device.hpp"]
+                  "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp"]
 SOURCE_FILES = [os.path.join(PKG_DIR, "csrc", f) for f in KERNEL_SOURCES] + \
                [os.path.join(os.path.dirname(PKG_DIR), "include", "rt_mi355x.h")]
 
@@ -176,6 +184,8 @@ def load_library(path=None):
     lib.rt_context_destroy.argtypes = [vp]
     lib.rt_context_set_scene.argtypes = [vp, P(RtScene)]
     lib.rt_render_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp]
+    lib.rt_render_split_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp, u32]
+    lib.rt_split_plan.argtypes = [u64, u32, u32, P(u32), P(u64)]
     lib.rt_context_collect.argtypes = [vp, vp, P(RtStats)]
     lib.rt_device_alloc.argtypes = [vp, ctypes.c_size_t, P(vp)]
     lib.rt_device_free.argtypes = [vp, vp]

@@ -43,6 +43,18 @@ class Renderer:
         raise NotImplementedError
 
 
+def split_argument(samples_per_item):
+    """render_flat's samples_per_item checked: None (rt_render_async), 0 (rt_render_split_async plans) or a
+    sample count (forced)."""
+    if samples_per_item is None:
+        return None
+    if isinstance(samples_per_item, bool) or not isinstance(samples_per_item, int):
+        raise TypeError(f"samples_per_item must be None or an int, not {samples_per_item!r}")
+    if samples_per_item < 0:
+        raise ValueError(f"samples_per_item must be >= 0, not {samples_per_item}")
+    return samples_per_item
+
+
 class GpuRenderer(Renderer):
     """Drop-in for TileRenderer: renders the whole image on one MI355X via rt_render_async.
 
@@ -51,18 +63,22 @@ class GpuRenderer(Renderer):
     mode: which reference renderer to reproduce — "vectorized2" (the live render_vectorized2,
     default), "vectorized" (render_vectorized), "vectorized3" (render_vectorized3) or "scalar" (render);
     see include/rt_mi355x.h.
+    sample_parallel: render() deals each pixel's samples to several waves where the frame has fewer pixels
+    than the chip has waves (rt_render_split_async's auto plan; the live path only, same image).
     """
 
     MODES = {"vectorized2": 0, "vectorized": abi.RT_FLAG_MODE_VECTORIZED, "vectorized3": abi.RT_FLAG_MODE_VECTORIZED3,
              "scalar": abi.RT_FLAG_MODE_SCALAR}
 
-    def __init__(self, device=0, seed=0x5EED0001, precision="f64", root2=False, mode="vectorized2", lib=None):
+    def __init__(self, device=0, seed=0x5EED0001, precision="f64", root2=False, mode="vectorized2", lib=None,
+                 sample_parallel=False):
         if mode not in self.MODES:
             raise ValueError(f"unknown mode {mode!r} (one of {sorted(self.MODES)})")
         if precision not in ("f64", "f32"):
             raise ValueError(f"unknown precision {precision!r}")
         self.lib = lib or abi.load_library()
         self.device = device
+        self.sample_parallel = bool(sample_parallel)
         self.seed = seed
         self.flags = ((abi.RT_FLAG_F32 if precision == "f32" else 0) | (abi.RT_FLAG_ROOT2 if root2 else 0)
                       | self.MODES[mode])
@@ -90,9 +106,12 @@ class GpuRenderer(Renderer):
         # allocated at a freed one's address, and the render would silently use the old spheres.
         self._scene_flat = flat
 
-    def render_flat(self, max_bounces, spp, flat, cam, tile_range=None, want_linear=False):
-        """Render with a FlatScene / RtCamera; returns (rgb [n,3] u8, linear [n,3] f64 | None, RtStats, rc)."""
+    def render_flat(self, max_bounces, spp, flat, cam, tile_range=None, want_linear=False, samples_per_item=None):
+        """Render with a FlatScene / RtCamera; returns (rgb [n,3] u8, linear [n,3] f64 | None, RtStats, rc).
+        samples_per_item: None = rt_render_async; 0 = rt_render_split_async with its own plan; n > 0 = that many
+        samples per work item (the sample-parallel path, include/rt_mi355x.h)."""
         lib = self.lib
+        split = split_argument(samples_per_item)
         if self._scene_flat is not flat:
             self.set_scene(flat)
         if tile_range is None:
@@ -105,8 +124,13 @@ class GpuRenderer(Renderer):
         try:
             if want_linear:
                 abi.check(lib, lib.rt_device_alloc(self.ctx, npx * 3 * 8, ctypes.byref(d_lin)))
-            abi.check(lib, lib.rt_render_async(self.ctx, ctypes.byref(cam), max_bounces, spp, self.seed, self.flags,
-                                               ctypes.byref(tr), d_rgb, d_lin if want_linear else None, None))
+            if split is None:
+                abi.check(lib, lib.rt_render_async(self.ctx, ctypes.byref(cam), max_bounces, spp, self.seed, self.flags,
+                                                   ctypes.byref(tr), d_rgb, d_lin if want_linear else None, None))
+            else:
+                abi.check(lib, lib.rt_render_split_async(self.ctx, ctypes.byref(cam), max_bounces, spp, self.seed,
+                                                         self.flags, ctypes.byref(tr), d_rgb,
+                                                         d_lin if want_linear else None, None, split))
             st = abi.RtStats()
             rc = abi.check(lib, lib.rt_context_collect(self.ctx, None, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
             rgb = np.empty((npx, 3), dtype=np.uint8)
@@ -125,7 +149,8 @@ class GpuRenderer(Renderer):
         t0 = time.perf_counter()
         flat = scene.flatten() if hasattr(scene, "flatten") else scene
         cam = camera.abi if hasattr(camera, "abi") else camera
-        rgb, _, st, rc = self.render_flat(max_bounces, samples_per_pixel, flat, cam)
+        rgb, _, st, rc = self.render_flat(max_bounces, samples_per_pixel, flat, cam,
+                                          samples_per_item=0 if self.sample_parallel else None)
         dt = time.perf_counter() - t0
         if rc == abi.RT_ERR_RANGE:
             raise abi.RtError(rc, "a pixel channel exceeded 2.0 (reference: Color::to_u8_array panics)")

@@ -12,7 +12,8 @@ def kernels(path):
     text = open(path).read()
     out = {}
     for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
-        body = re.sub(r"\.LBB\d+_\d+", "L", m.group(2))
+        # (also in the "in Loop: Header=BB12_3" comments: the function's number shifts when kernels are added)
+        body = re.sub(r"(?:\.L)?BB\d+_\d+", "L", m.group(2))
         body = re.sub(r"\.Ltmp\d+", "T", body)
         body = re.sub(r"\.Lfunc_end\d+", "E", body)
         out[m.group(1)] = body
