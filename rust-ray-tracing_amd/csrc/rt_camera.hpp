@@ -501,6 +501,12 @@ __global__ void build_cam_table(const T* sph, T* cam, uint32_t n_slots, float* c
         float* out = camf + 16 * fg + 8 * (fj / 2) + (fj % 2);
         out[0] = (float)ocx; out[2] = (float)ocy; out[4] = (float)ocz; out[6] = sc;
     }
+    // cone() (cone_walk) squares a record's w in fp32: t = w.a, p = |w x a| = sqrt(px^2 + py^2 + pz^2).  Past
+    // |w| = 1.8e19 the sum is +inf, f = p cos - t sin = +inf > rp and a sphere in full view was culled (an fp64
+    // render of a scene scaled by 1e19: every primary ray missed everything).  Records with |w| >= kConeWMax get
+    // rp = +inf, "always tested" (f > +inf is false, NaN passes): a cluster's members are then tested one by
+    // one, a sphere goes to the exact test.
+    constexpr double kConeWMax = 1e18;
     auto rup = [](double v) -> float {   // fp32 >= v; +inf past 1e30 (and for NaN)
         if (!(v < 1e30)) return INFINITY;
         float f = (float)v;
@@ -525,7 +531,8 @@ __global__ void build_cam_table(const T* sph, T* cam, uint32_t n_slots, float* c
             ex = ox - cx; ey = oy - cy; ez = oz - cz;
             ec = SCALAR ? ((ex * ex + ey * ey) + ez * ez) - r2 : fma(ez, ez, fma(ey, ey, ex * ex)) - r2;
             const double wn2 = (double)ex * (double)ex + (double)ey * (double)ey + (double)ez * (double)ez;
-            rp = pass_all ? INFINITY
+            // |w| of 1e18 or more: the cone test's fp32 |w x a|^2 could overflow to +inf and cull (kConeWMax)
+            rp = pass_all || !(wn2 < kConeWMax * kConeWMax) ? INFINITY
                           : rup(sqrt((double)r2 * (1.0 + 0x1.0p-20) + 0x1.0p-18 * wn2) + 0x1.0p-19 * sqrt(wn2) + 1e-30);
             w[0] = -(float)ex; w[1] = -(float)ey; w[2] = -(float)ez;   // c - O = -(O - c) exactly
         }
@@ -542,7 +549,8 @@ __global__ void build_cam_table(const T* sph, T* cam, uint32_t n_slots, float* c
         if (R > -INFINITY) {
             const double wx = clus[4 * i] - (double)ox, wy = clus[4 * i + 1] - (double)oy, wz = clus[4 * i + 2] - (double)oz;
             const double wn = sqrt(wx * wx + wy * wy + wz * wz);
-            rp = pass_all ? INFINITY : rup(R * (1.0 + 0x1.0p-20) + (0x1.0p-9 + 0x1.0p-16) * (wn + R) + 1e-30);
+            rp = pass_all || !(wn < kConeWMax) ? INFINITY
+                                               : rup(R * (1.0 + 0x1.0p-20) + (0x1.0p-9 + 0x1.0p-16) * (wn + R) + 1e-30);
             w[0] = (float)wx; w[1] = (float)wy; w[2] = (float)wz;
         }
         cullc[4 * i] = w[0]; cullc[4 * i + 1] = w[1]; cullc[4 * i + 2] = w[2]; cullc[4 * i + 3] = rp;
