@@ -216,6 +216,51 @@ int rt_render_split_async(rt_context* ctx, const rt_camera* camera, uint32_t max
  * than 0x7FFFFFFF items. */
 int rt_split_plan(uint64_t n_pixels, uint32_t spp, uint32_t resident_waves, uint32_t* samples_per_item,
                   uint64_t* n_items);
+/* ---- progressive sessions: add samples to a frame, take an image at any count ----
+ * A session keeps every sample's record (primary y, colour, termination bounce) in a record buffer of its own,
+ * laid out for spp_capacity samples per pixel: 17 bytes per sample of capacity in fp32, 33 in fp64 (36 / 68
+ * when max_bounces > 254), per pixel rounded up to 256 bytes.  1920x1080 at 512 spp is 18.0 GB in fp32 and
+ * 35.0 GB in fp64.  The RNG is keyed by (pixel, sample, bounce), so a sample's record does not depend on how
+ * many samples its pixel will have, and the image after n samples is bit for bit rt_render_async's at spp = n
+ * with the same arguments, for every n; going from n to m traces only the m - n new samples.
+ * The live path only (flags: RT_FLAG_F32 or 0).  One session per context; rt_render_async and
+ * rt_render_split_async may be interleaved with it on the same context (they share the counter, scratch and
+ * camera tables under rt_render_async's cross-stream rule and never touch the session's records). */
+
+/* Host only, needs no GPU: the bytes of record buffer a session needs, n_pixels regions of
+ * spp_capacity rounded up to 4 samples.  RT_ERR_INVALID: NULL output, no pixels, spp_capacity == 0, unknown
+ * flag bits; RT_ERR_UNSUPPORTED: spp_capacity > 2^20, more than 0x7FFFFFFF pixels, RT_FLAG_ROOT2 or a
+ * RT_FLAG_MODE_*. */
+int rt_progressive_bytes(uint64_t n_pixels, uint32_t spp_capacity, uint32_t max_bounces, uint32_t flags,
+                         uint64_t* bytes);
+/* Open a session on ctx: fixes the camera, max_bounces, seed, flags, range (NULL = whole image) and
+ * spp_capacity and allocates the record buffer.  max_bytes: the most it may allocate; 0 = the library's
+ * scratch budget (24 GB).  Synchronous.
+ * RT_ERR_INVALID: a session is already open, spp_capacity == 0, unknown flag bits, a bad range;
+ * RT_ERR_UNSUPPORTED: a flag other than RT_FLAG_F32, spp_capacity > 2^20, fp32 with max_bounces >
+ * RT_MAX_BOUNCES_F32, more than 0x7FFFFFFF pixels (an extend has one work item per pixel at least), a record
+ * buffer over max_bytes.  While a session is open rt_context_set_scene is RT_ERR_INVALID (the records belong
+ * to the scene they were traced in). */
+int rt_progressive_begin(rt_context* ctx, const rt_camera* camera, uint32_t max_bounces, uint32_t spp_capacity,
+                         uint64_t seed, uint32_t flags, const rt_tile_range* range, uint64_t max_bytes);
+/* Trace samples [done, spp_total) of every pixel (done: the spp_total of the previous extend, 0 at first),
+ * then, if d_rgb8 or d_linear is non-NULL, reduce samples [0, spp_total) into them.  Asynchronous on `stream`,
+ * same cross-stream rule as rt_render_async.  The window is planned like rt_split_plan(pixels, spp_total -
+ * done, resident waves) and always runs the sample-parallel kernels.
+ *   spp_total == done with an output: a snapshot (the reduction only).
+ *   spp_total > done with both outputs NULL: tracing only.
+ *   spp_total == done with both outputs NULL: RT_OK, nothing is enqueued.
+ * RT_ERR_INVALID: no session open, spp_total == 0, below done or above spp_capacity.
+ * rt_context_collect after it: the outputs and the return code (RT_ERR_RANGE included) are those of
+ * rt_render_async at spp = spp_total.  samples and ray_segments count the samples traced since the last
+ * collect, so their sums over a session's collects up to n equal the unsplit render's at spp = n;
+ * bounce_iters gets every pixel's K once per reduction, pixels the pixel count once per extend that enqueued
+ * work; RT_KERNEL_SPLIT(kernel_id) is set and kernel_ms covers the trace and reduction kernels. */
+int rt_progressive_extend_async(rt_context* ctx, uint32_t spp_total, void* d_rgb8, void* d_linear, void* stream);
+/* Close the session: synchronises the stream of its last extend and frees the record buffer.
+ * RT_ERR_INVALID: no session open.  rt_context_destroy ends an open session. */
+int rt_progressive_end(rt_context* ctx);
+
 /* RenderStat (renderer.rs:11-34) for the renders since the last call.
  * Synchronise `stream` (NULL = null stream), then report and reset the counters accumulated by the renders
  * enqueued since the last call (ray_segments, work counters, error flag).  kernel_ms = device time

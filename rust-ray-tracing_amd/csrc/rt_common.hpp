@@ -143,6 +143,19 @@ template <typename T> struct SParams {
     uint32_t n_pix;            // pixels of the rendered set (k.n_items / nsub)
 };
 
+// Arguments of a progressive session's kernels (trace_paths_window, finish_window;
+// rt_progressive_extend_async): SParams first, at the same kernarg offsets, then the session's own.
+//   * The trace launch covers the sample window [s_begin, s.k.spp) of every pixel: item i is pixel i / nsub and,
+//     j = i % nsub, samples [max(s_begin, s_base + j S), min(s.k.spp, s_base + (j + 1) S)) (rt_progressive_plan.hpp).
+//     Its s.k.P and s.k.sbytes are the session's capacity (the strides of a region).
+//   * The finish launch reduces the prefix [0, s.k.spp): s.k.spp, P, C, s_sel, vbytes and bit 1 of swide are
+//     the snapshot's, P_cap and s.k.sbytes the capacity's.
+template <typename T> struct WParams {
+    SParams<T> s;
+    uint32_t s_begin, s_base;
+    uint32_t P_cap;            // positions a region is laid out for: y[P_cap], c[P_cap], e[P_cap]
+};
+
 constexpr int kSegShards = 256;
 constexpr uint32_t kFlagPinholeInternal = 0x80000000u;   // set by the host: defocus vectors are +-0
 constexpr int kWavesF32 = 6;   // default min-waves-per-SIMD targets (measured sweep);
@@ -206,6 +219,12 @@ template <typename T> __device__ __forceinline__ cptr<KParams<T>> cold_args() {
 // The sample-parallel kernels' whole argument struct, read the same way.
 template <typename T> __device__ __forceinline__ cptr<SParams<T>> cold_split_args() {
     cptr<SParams<T>> k = (cptr<SParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+// ... and a progressive session's.
+template <typename T> __device__ __forceinline__ cptr<WParams<T>> cold_window_args() {
+    cptr<WParams<T>> k = (cptr<WParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));
     return k;
 }

@@ -97,6 +97,10 @@ template <typename T> __device__ __forceinline__ PScratch<T> wave_scratch(uint32
 // formats, indexed by the absolute sample id.  The `s` every accessor takes is the pixel's index in the
 // set (not a wave's slot) and the region's offset is formed in 64 bits.  base: the position map of the
 // wave that reduces the pixel (finish_records; the trace kernels never touch it).
+// P and sbytes are the layout of a region (y[P], c[P], e[P]), not the pixel's sample count: finish_pixel takes
+// spp, P, C and s_sel from the kernel arguments.  A progressive session's regions are laid out for its
+// capacity (P = P_cap) and reduced at any count up to it; wide bit 1 (the map) then follows the count, bit 0
+// (the width of e) the session's depth.
 template <typename T> struct RScratch {
     char* base;        // wave-uniform
     char* rec;

@@ -30,11 +30,13 @@
 // Source layout (one translation unit): rt_experiments.hpp (build kinds), rt_common.hpp (layouts,
 // kernel arguments, scalar-load pipelines), rt_sweep.hpp (general sweep), rt_camera.hpp (primary
 // rays, scatter), rt_finish.hpp (replay + reduction), rt_trace.hpp + rt_trace_body.hpp (the persistent kernel),
-// rt_layout.hpp (host-side scene layout), rt_split_plan.hpp (the sample-parallel plan, host only); this
+// rt_layout.hpp (host-side scene layout), rt_split_plan.hpp (the sample-parallel plan, host only),
+// rt_progressive_plan.hpp (a progressive session's record buffer and sample windows, host only); this
 // file holds the C ABI.
 #include "rt_trace.hpp"
 #include "rt_layout.hpp"
 #include "rt_split_plan.hpp"
+#include "rt_progressive_plan.hpp"
 
 #include <chrono>
 #include <mutex>
@@ -109,6 +111,19 @@ struct rt_context {
     struct CamKey { bool valid = false; uint64_t gen = 0; double center[3] = {0, 0, 0}; uint32_t scalar = 0, off = 0; };
     CamKey camkey[2];   // [0] fp32 tables, [1] fp64
     uint32_t last_kernel_id = 0, last_wg_per_cu = 0;   // rt_stats.kernel_id / kernel_wg_per_cu of the last launch
+    // The progressive session (rt_progressive_*): what rt_progressive_begin fixed, the samples every pixel's
+    // region holds so far, and the record buffer, which only the session's launches touch.
+    struct Session {
+        bool open = false;
+        rt_camera cam{};
+        rt_tile_range rg{};
+        uint32_t depth = 0, cap = 0, flags = 0, done = 0;
+        uint64_t seed = 0;
+        void* rec = nullptr;
+        uint64_t bytes = 0;
+        hipStream_t stream = nullptr;   // of the last extend that enqueued work
+        bool have_stream = false;
+    } prog;
 };
 
 extern "C" const char* rt_last_error(void) { return g_err.c_str(); }
@@ -211,6 +226,7 @@ extern "C" int rt_context_destroy(rt_context* c) {
     if (!c) return RT_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    if (c->prog.open) (void)rt_progressive_end(c);
     free_scene(c);
     (void)hipFree(c->segs); (void)hipFree(c->err); (void)hipFree(c->counter); (void)hipFree(c->scratch);
     (void)hipFree(c->records);
@@ -222,6 +238,9 @@ extern "C" int rt_context_destroy(rt_context* c) {
 
 extern "C" int rt_context_set_scene(rt_context* c, const rt_scene* s) {
     if (!c || !s) return fail(RT_ERR_INVALID, "rt_context_set_scene: NULL argument");
+    if (c->prog.open)
+        return fail(RT_ERR_INVALID, "rt_context_set_scene: a progressive session is open (its records belong to the "
+                                    "current scene; rt_progressive_end first)");
     if (s->n_spheres && (!s->center || !s->radius || !s->material || !s->materials))
         return fail(RT_ERR_INVALID, "rt_context_set_scene: NULL array");
     for (uint32_t i = 0; i < s->n_spheres; ++i)
@@ -477,8 +496,22 @@ static SplitPick<T> pick_split(bool mega) {
                         (mega ? 1u << 8 : 0u) | (1u << 9);
     return SplitPick<T>{mega ? trace_paths_split<T, W, CAMQ, true> : trace_paths_split<T, W, CAMQ, false>, id, W};
 }
+// A progressive session's tracing kernel (trace_paths_window), at the same occupancy.
+template <typename T, bool CAMQ>
+static void (*pick_window(bool mega))(WParams<T>) {
+    constexpr int W = kWavesSplit<T>;
+    return mega ? trace_paths_window<T, W, CAMQ, true> : trace_paths_window<T, W, CAMQ, false>;
+}
 // A render's split: S samples per work item, nsub items per pixel (rt_split_plan.hpp).
-struct SplitShape { uint32_t S, nsub; };
+// rec != nullptr: one extend of a progressive session (rt_progressive_plan.hpp).  The launch's spp is the
+// session's new sample count: the trace kernel (trace) covers the window [s_begin, spp) on the item grid
+// s_base + j S, writing regions laid out for cap samples in rec, and finish_window (finish) reduces [0, spp).
+struct SplitShape {
+    uint32_t S, nsub;
+    char* rec = nullptr;
+    uint32_t s_begin = 0, s_base = 0, cap = 0;
+    bool trace = true, finish = true;
+};
 constexpr uint64_t kScratchBudget = 24ull << 30;   // scratch (and record buffer) bytes a launch may ask for
 
 // split: the sample-parallel path (trace_paths_split over (pixel, sample sub-range) items, then
@@ -596,7 +629,9 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
                                     : pick_kernel<T, false>(flags, W, p.n_mg > 0, big);
     void (*kern)(KParams<T>) = pick.fn;
     const SplitPick<T> spick = camq ? pick_split<T, true>(p.n_mg > 0) : pick_split<T, false>(p.n_mg > 0);
-    const void* const kfn = split ? (const void*)spick.fn : (const void*)kern;
+    void (*const wfn)(WParams<T>) = camq ? pick_window<T, true>(p.n_mg > 0) : pick_window<T, false>(p.n_mg > 0);
+    const bool session = split && split->rec != nullptr;
+    const void* const kfn = session ? (const void*)wfn : split ? (const void*)spick.fn : (const void*)kern;
     const int kW = split ? spick.W : pick.W;
     if (camq) {
         p.camsph = (const T*)(f64 ? c->cam64 : c->cam32);
@@ -649,7 +684,8 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
     {   // G: the largest power of two <= min(kMaxBlock, kBlockSamples / spp, pixels per wave / kBlockShare),
         // raised to kClaimSpp / spp (claim rate, below) where the share bound would go under it
         // (the sample-parallel path: an item's samples for spp, items for pixels)
-        const uint32_t ispp = split ? std::min(split->S, spp) : spp;
+        const uint32_t ispp = session ? std::max(1u, std::min(split->S, spp - split->s_begin))
+                                      : split ? std::min(split->S, spp) : spp;
         const uint64_t per_wave = (uint64_t)p.n_items / (4u * nblocks);
         const uint64_t g = std::max<uint64_t>({1u, std::min<uint64_t>({(uint64_t)kMaxBlock, kBlockSamples / ispp,
                                                                        per_wave / kBlockShare}),
@@ -670,17 +706,41 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
         p.scratch_stride = (size_t)p.vbytes;
         uint64_t fblocks = std::min<uint64_t>(((uint64_t)n_pix + 3) / 4, (uint64_t)c->n_cu * 8u);
         fblocks = std::max<uint64_t>(1u, std::min<uint64_t>(fblocks, kScratchBudget / (4 * p.scratch_stride)));
-        int rc = ensure_records(c, (size_t)n_pix * p.sbytes, st);
+        // a session's regions keep the layout of its capacity whatever the count (the width of e, bit 0 of
+        // swide, depends on the depth alone)
+        const uint32_t P_cap = session ? 4u * ((split->cap + 3u) / 4u) : p.P;
+        if (session) p.sbytes = paths_sbytes(P_cap, sizeof(T), p.swide);
+        int rc = session ? RT_OK : ensure_records(c, (size_t)n_pix * p.sbytes, st);
         if (rc == RT_OK) rc = ensure_scratch(c, p.scratch_stride * fblocks * 4, st);
         if (rc != RT_OK) return rc;
         p.scratch = (char*)c->scratch;
         SParams<T> sp;
         memset(&sp, 0, sizeof(sp));
         sp.k = p;
-        sp.rec = (char*)c->records;
+        sp.rec = session ? split->rec : (char*)c->records;
         sp.S = split->S;
         sp.nsub = split->nsub;
         sp.n_pix = n_pix;
+        if (session) {
+            WParams<T> wp;
+            memset(&wp, 0, sizeof(wp));
+            wp.s = sp;   // the snapshot's counts: finish_window
+            wp.s_begin = split->s_begin;
+            wp.s_base = split->s_base;
+            wp.P_cap = P_cap;
+            if (split->trace) {
+                WParams<T> wt = wp;
+                wt.s.k.P = P_cap;   // the record view's stride (split_records); the trace kernels read no other count
+                HIPCHK(hipMemsetAsync(c->counter, 0, kStreams * kCtrStride * sizeof(uint32_t), st));
+                hipLaunchKernelGGL(wfn, dim3((uint32_t)nblocks), dim3(256), 0, st, wt);
+                HIPCHK(hipGetLastError());
+            }
+            if (split->finish) {
+                hipLaunchKernelGGL(finish_window<T>, dim3((uint32_t)fblocks), dim3(256), 0, st, wp);
+                HIPCHK(hipGetLastError());
+            }
+            return RT_OK;
+        }
         HIPCHK(hipMemsetAsync(c->counter, 0, kStreams * kCtrStride * sizeof(uint32_t), st));
         hipLaunchKernelGGL(spick.fn, dim3((uint32_t)nblocks), dim3(256), 0, st, sp);
         HIPCHK(hipGetLastError());
@@ -810,6 +870,120 @@ extern "C" int rt_split_plan(uint64_t n_pixels, uint32_t spp, uint32_t resident_
                              uint64_t* n_items) {
     const int rc = split_plan(n_pixels, spp, resident_waves, samples_per_item, n_items);
     if (rc != kPlanOk) return fail(rc, "rt_split_plan: no plan (NULL output, no pixels or samples, spp > 2^20 or too many items)");
+    return RT_OK;
+}
+
+// ---- progressive sessions (rt_progressive_plan.hpp) ----
+extern "C" int rt_progressive_bytes(uint64_t n_pixels, uint32_t spp_capacity, uint32_t max_bounces, uint32_t flags,
+                                    uint64_t* bytes) {
+    const int rc = progressive_bytes(n_pixels, spp_capacity, max_bounces, flags, bytes);
+    if (rc != kPlanOk)
+        return fail(rc, "rt_progressive_bytes: NULL output, no pixels or samples, an unknown flag (invalid); "
+                        "spp_capacity > 2^20, more than 0x7FFFFFFF pixels or a flag other than RT_FLAG_F32 (unsupported)");
+    return RT_OK;
+}
+
+extern "C" int rt_progressive_begin(rt_context* c, const rt_camera* cam, uint32_t max_bounces, uint32_t spp_capacity,
+                                    uint64_t seed, uint32_t flags, const rt_tile_range* range, uint64_t max_bytes) {
+    const std::string who = "rt_progressive_begin";
+    if (!c || !cam) return fail(RT_ERR_INVALID, who + ": NULL argument");
+    if (c->prog.open) return fail(RT_ERR_INVALID, who + ": a session is already open on this context");
+    if (spp_capacity == 0) return fail(RT_ERR_INVALID, who + ": spp_capacity == 0");
+    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
+    if (flags & ~RT_FLAG_F32) return fail(RT_ERR_UNSUPPORTED, who + ": the live path only (no RT_FLAG_ROOT2, no RT_FLAG_MODE_*)");
+    if (spp_capacity > (1u << 20)) return fail(RT_ERR_UNSUPPORTED, who + ": spp_capacity > 2^20");
+    if ((flags & RT_FLAG_F32) && max_bounces > RT_MAX_BOUNCES_F32)
+        return fail(RT_ERR_UNSUPPORTED, who + ": fp32 with max_bounces > RT_MAX_BOUNCES_F32 (3839)");
+    if (cam->image_width == 0 || cam->image_height == 0) return fail(RT_ERR_INVALID, who + ": empty image");
+    if ((uint64_t)cam->image_width * cam->image_height > 0xFFFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": image too large");
+    const rt_tile_range rg = range ? *range : rt_tile_range{0, 1, cam->image_height, 0, cam->image_width};
+    if (!check_range(cam, &rg)) return fail(RT_ERR_INVALID, who + ": tile range outside the image");
+    const uint64_t n_pix = (uint64_t)rg.row_count * rg.col_count;
+    // an extend has one work item per pixel at least
+    if (n_pix > kSplitMaxItems) return fail(RT_ERR_UNSUPPORTED, who + ": more than 0x7FFFFFFF work items in one extend");
+    uint64_t bytes = 0;
+    const int prc = progressive_bytes(n_pix, spp_capacity, max_bounces, flags, &bytes);
+    if (prc != kPlanOk) return fail(prc, who + ": no record buffer for this shape");
+    const uint32_t P_cap = prog_positions(spp_capacity), tsz = (flags & RT_FLAG_F32) ? 4u : 8u;
+    if (bytes != n_pix * paths_sbytes(P_cap, tsz, paths_wide(P_cap, max_bounces)))
+        return fail(RT_ERR_INVALID, who + ": internal: rt_progressive_plan.hpp and rt_finish.hpp disagree on a region's size");
+    const uint64_t limit = max_bytes ? max_bytes : kScratchBudget;
+    if (bytes > limit)
+        return fail(RT_ERR_UNSUPPORTED, who + ": the record buffer (" + std::to_string(bytes) + " bytes) is over " +
+                                            (max_bytes ? "max_bytes" : "the scratch budget; pass max_bytes"));
+    HIPCHK(hipSetDevice(c->device));
+    void* rec = nullptr;
+    HIPCHK(hipMalloc(&rec, (size_t)bytes));
+    rt_context::Session& s = c->prog;
+    s = rt_context::Session{};
+    s.open = true;
+    s.cam = *cam;
+    s.rg = rg;
+    s.depth = max_bounces;
+    s.cap = spp_capacity;
+    s.flags = flags;
+    s.seed = seed;
+    s.rec = rec;
+    s.bytes = bytes;
+    return RT_OK;
+}
+
+extern "C" int rt_progressive_extend_async(rt_context* c, uint32_t spp_total, void* d_rgb8, void* d_linear, void* stream) {
+    const std::string who = "rt_progressive_extend_async";
+    if (!c) return fail(RT_ERR_INVALID, who + ": NULL context");
+    rt_context::Session& s = c->prog;
+    if (!s.open) return fail(RT_ERR_INVALID, who + ": no session open on this context");
+    if (spp_total == 0) return fail(RT_ERR_INVALID, who + ": spp_total == 0");
+    if (spp_total < s.done) return fail(RT_ERR_INVALID, who + ": spp_total below the samples already traced");
+    if (spp_total > s.cap) return fail(RT_ERR_INVALID, who + ": spp_total above the session's spp_capacity");
+    const bool f32 = (s.flags & RT_FLAG_F32) != 0;
+    const uint64_t n_pix = (uint64_t)s.rg.row_count * s.rg.col_count;
+    SplitShape shape{1u, 1u};
+    shape.rec = (char*)s.rec;
+    shape.cap = s.cap;
+    shape.trace = spp_total > s.done;
+    shape.finish = d_rgb8 != nullptr || d_linear != nullptr;
+    shape.s_begin = shape.s_base = s.done;
+    if (!shape.trace && !shape.finish) return RT_OK;
+    if (shape.trace) {
+        const uint32_t waves = (uint32_t)c->n_cu * 4u * (uint32_t)(f32 ? kWavesSplit<float> : kWavesSplit<double>);
+        ProgWindow w;
+        const int prc = progressive_window(n_pix, s.done, spp_total, waves, &w);
+        if (prc != kPlanOk) return fail(prc, who + ": no plan for this window (more than 0x7FFFFFFF work items)");
+        shape.S = w.S;
+        shape.nsub = w.nsub;
+        shape.s_base = w.base;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    // the serialisation rule of render_async: the session shares the counter, scratch and camera tables
+    if (c->have_last && c->last_stream != st) HIPCHK(hipStreamSynchronize(c->last_stream));
+    c->last_stream = st;
+    c->have_last = true;
+    if (!c->have_first) {
+        HIPCHK(hipEventRecord(c->ev_first, st));
+        c->have_first = true;
+    }
+    const int rc = f32 ? launch_t<float>(c, &s.cam, s.depth, spp_total, s.seed, s.flags, s.rg, d_rgb8, d_linear, st, &shape)
+                       : launch_t<double>(c, &s.cam, s.depth, spp_total, s.seed, s.flags, s.rg, d_rgb8, d_linear, st, &shape);
+    if (rc != RT_OK) return rc;
+    HIPCHK(hipEventRecord(c->ev_last, st));
+    c->pixels += n_pix;
+    c->samples += n_pix * (uint64_t)(spp_total - s.done);
+    s.done = spp_total;
+    s.stream = st;
+    s.have_stream = true;
+    return RT_OK;
+}
+
+extern "C" int rt_progressive_end(rt_context* c) {
+    if (!c) return fail(RT_ERR_INVALID, "rt_progressive_end: NULL context");
+    rt_context::Session& s = c->prog;
+    if (!s.open) return fail(RT_ERR_INVALID, "rt_progressive_end: no session open on this context");
+    HIPCHK(hipSetDevice(c->device));
+    if (s.have_stream) HIPCHK(hipStreamSynchronize(s.stream));
+    HIPCHK(hipFree(s.rec));
+    s = rt_context::Session{};
     return RT_OK;
 }
 

@@ -1,0 +1,84 @@
+// rt_progressive_plan.hpp — the host arithmetic of a progressive session (rt_progressive_*): the record
+// buffer a session of a given sample capacity needs, and how one extend's sample window [done, spp_total)
+// is dealt into work items.  Pure host C++ (no HIP): the library and the stand-alone sanitizer program
+// tests/sanitize/progressive_plan_san.cpp include it.
+#pragma once
+#include <stdint.h>
+
+#include "rt_split_plan.hpp"
+
+namespace rt {
+
+constexpr uint32_t kProgFlagF32 = 0x1u, kProgFlagAll = 0x1Fu;   // RT_FLAG_F32, RT_FLAG_ALL (include/rt_mi355x.h)
+
+// Positions of a pixel of `spp` samples: whole chunks of 4 (PackedRays<4>).
+inline uint32_t prog_positions(uint32_t spp) { return 4u * ((spp + 3u) / 4u); }
+
+// One pixel's region of the record buffer at P_cap positions: y[P] (T), c[P] (3 T), e[P] (u8; u32 when
+// max_bounces > 254), rounded up to 256 bytes.  The value of paths_sbytes(P, tsz, paths_wide(P, depth))
+// (rt_finish.hpp; rt_progressive_begin checks that they agree).
+inline uint32_t prog_region_bytes(uint32_t P_cap, uint32_t tsz, uint32_t max_bounces) {
+    const uint32_t esz = max_bounces > 254u ? 4u : 1u;
+    return (P_cap * (4u * tsz + esz) + 255u) & ~255u;   // P_cap <= 2^20, 36 bytes each: below 2^26
+}
+
+// rt_progressive_bytes.  17 bytes per sample of capacity in fp32, 33 in fp64 (u8 e).
+inline int progressive_bytes(uint64_t n_pixels, uint32_t spp_capacity, uint32_t max_bounces, uint32_t flags,
+                             uint64_t* bytes) {
+    if (!bytes) return kPlanInvalid;
+    *bytes = 0;
+    if (n_pixels == 0 || spp_capacity == 0) return kPlanInvalid;
+    if (flags & ~kProgFlagAll) return kPlanInvalid;   // as rt_render_split_async: unknown bits are invalid,
+    if (flags & ~kProgFlagF32) return kPlanUnsupported;   // RT_FLAG_ROOT2 and RT_FLAG_MODE_* unsupported
+    if (spp_capacity > kSplitMaxSpp || n_pixels > kSplitMaxItems) return kPlanUnsupported;
+    const uint32_t tsz = (flags & kProgFlagF32) ? 4u : 8u;
+    *bytes = n_pixels * prog_region_bytes(prog_positions(spp_capacity), tsz, max_bounces);   // < 2^31 x 2^26
+    return kPlanOk;
+}
+
+// One extend's items.  Item i is pixel i / nsub and, with j = i % nsub, the samples
+//   [max(done, base + j S), min(spp_total, base + (j + 1) S)).
+// Where S is a multiple of kSplitGrain, base is `done` rounded down to the grain, so every item boundary but
+// the window's own ends is an absolute multiple of 128 (a short first item): no two items of a launch share a
+// 128-byte line of a pixel's u8 e array, as in rt_render_split_async.  Any other S (the one-item-per-pixel
+// plan, whose S is the window itself) starts at `done`.
+struct ProgWindow {
+    uint32_t S, nsub, base;
+    uint64_t n_items;
+};
+
+inline void prog_item(const ProgWindow& w, uint32_t done, uint32_t spp_total, uint32_t j, uint32_t* first,
+                      uint32_t* end) {
+    const uint32_t a = w.base + j * w.S, b = a + w.S;   // <= spp_total + S <= 2^21
+    *first = a > done ? a : done;
+    *end = b < spp_total ? b : spp_total;
+}
+
+// The window [done, spp_total) in items of S samples (S >= 1, done < spp_total <= 2^20).
+inline int progressive_window_s(uint64_t n_pixels, uint32_t done, uint32_t spp_total, uint32_t S, ProgWindow* w) {
+    if (!w) return kPlanInvalid;
+    *w = ProgWindow{0u, 0u, 0u, 0u};
+    if (n_pixels == 0 || S == 0 || spp_total <= done) return kPlanInvalid;
+    if (spp_total > kSplitMaxSpp || S > kSplitMaxSpp || n_pixels > kSplitMaxItems) return kPlanUnsupported;
+    const uint32_t base = S % kSplitGrain == 0u ? done - done % kSplitGrain : done;
+    const uint32_t nsub = split_nsub(spp_total - base, S);
+    const uint64_t items = n_pixels * nsub;   // < 2^31 x 2^20
+    if (items > kSplitMaxItems) return kPlanUnsupported;
+    *w = ProgWindow{S, nsub, base, items};
+    return kPlanOk;
+}
+
+// The plan of rt_progressive_extend_async: split_plan over the window's samples.
+inline int progressive_window(uint64_t n_pixels, uint32_t done, uint32_t spp_total, uint32_t resident_waves,
+                              ProgWindow* w) {
+    if (!w) return kPlanInvalid;
+    *w = ProgWindow{0u, 0u, 0u, 0u};
+    if (spp_total <= done) return kPlanInvalid;
+    uint32_t S = 0;
+    uint64_t n = 0;
+    const int rc = split_plan(n_pixels, spp_total - done, resident_waves, &S, &n);
+    if (rc != kPlanOk) return rc;
+    return progressive_window_s(n_pixels, done, spp_total, S, w);
+}
+
+}  // namespace rt

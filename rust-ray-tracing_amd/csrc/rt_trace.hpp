@@ -89,7 +89,7 @@ template <typename T, bool B> constexpr bool kSplitKernel = B;
 
 template <typename T, int W, bool ROOT2, int MODE = kModeV2, bool CAMQ = false, bool MEGA = false>
 __global__ __launch_bounds__(256, W) void trace_paths(KParams<T> p) {
-    constexpr bool SPLIT = kSplitKernel<T, false>;
+    constexpr bool SPLIT = kSplitKernel<T, false>, WIN = kSplitKernel<T, false>;
 #include "rt_trace_body.hpp"
 }
 
@@ -97,9 +97,20 @@ __global__ __launch_bounds__(256, W) void trace_paths(KParams<T> p) {
 // over (pixel, sample sub-range) items; finish_records follows it on the same stream.
 template <typename T, int W, bool CAMQ, bool MEGA>
 __global__ __launch_bounds__(256, W) void trace_paths_split(SParams<T> sp) {
-    constexpr bool SPLIT = kSplitKernel<T, true>, ROOT2 = false;
+    constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, false>, ROOT2 = false;
     constexpr int MODE = kModeV2;
     const KParams<T>& p = sp.k;
+#include "rt_trace_body.hpp"
+}
+
+// A progressive session's tracing kernel (rt_progressive_extend_async): trace_paths_split with WIN, its items
+// tiling the sample window [s_begin, spp) of every pixel, the regions laid out for the session's capacity
+// (WParams).  Kernels of their own beside trace_paths_split, whose code, names and arguments stay as they were.
+template <typename T, int W, bool CAMQ, bool MEGA>
+__global__ __launch_bounds__(256, W) void trace_paths_window(WParams<T> wp) {
+    constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, true>, ROOT2 = false;
+    constexpr int MODE = kModeV2;
+    const KParams<T>& p = wp.s.k;
 #include "rt_trace_body.hpp"
 }
 
@@ -118,6 +129,31 @@ __global__ __launch_bounds__(256) void finish_records(SParams<T> sp) {
     const auto& q = *cold_split_args<T>();
     const uint32_t gw = blockIdx.x * 4u + wave, nw = gridDim.x * 4u;
     const RScratch<T> sc{q.k.scratch + (size_t)gw * q.k.scratch_stride, q.rec, q.k.P, q.k.sbytes, q.k.swide};
+    const uint32_t n_pix = q.n_pix;
+    unsigned long long iters = 0;
+    for (uint64_t px = gw; px < n_pix; px += nw) {
+        iters += finish_pixel<T, kModeV2, true>(sc, (uint32_t)px, (uint32_t)px, s_hist[wave], s_stage[wave],
+                                                kLMapCap > 0u ? s_lmap[wave] : nullptr, false);
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (lane == 0 && iters != 0ull) atomicAdd(&q.k.segs[(gw & (kSegShards - 1)) * kSegStride + 2], iters);
+}
+
+// A session's snapshot: finish_records over the prefix [0, spp) of regions laid out for P_cap positions.  The
+// counts (spp, P, C, s_sel, the map's width and bytes) in the KParams are the snapshot's, which finish_pixel
+// reads as ever; only the record view's stride is the capacity's.  Samples at and past spp, traced by an
+// earlier, longer extend or not at all, are never read.
+template <typename T>
+__global__ __launch_bounds__(256) void finish_window(WParams<T> wp) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][64];
+    __shared__ __attribute__((aligned(16))) T s_stage[4][3][64];
+    __shared__ __attribute__((aligned(16))) uint16_t s_lmap[4][kLMapCap > 0u ? kLMapCap : 2];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const auto& q = *cold_split_args<T>();
+    const uint32_t gw = blockIdx.x * 4u + wave, nw = gridDim.x * 4u;
+    const RScratch<T> sc{q.k.scratch + (size_t)gw * q.k.scratch_stride, q.rec, cold_window_args<T>()->P_cap, q.k.sbytes,
+                         q.k.swide};
     const uint32_t n_pix = q.n_pix;
     unsigned long long iters = 0;
     for (uint64_t px = gw; px < n_pix; px += nw) {

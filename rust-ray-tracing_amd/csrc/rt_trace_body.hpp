@@ -1,6 +1,7 @@
 // rt_trace_body.hpp -- the statements of the persistent path-regeneration kernel, included as the body of
 // trace_paths and of trace_paths_split (rt_trace.hpp; not a header on its own).  In scope: T, W, ROOT2, MODE,
-// CAMQ, MEGA, SPLIT and the kernel arguments p (KParams<T>).
+// CAMQ, MEGA, SPLIT, WIN (SPLIT only: the items tile a sample window, WParams<T>) and the kernel arguments p
+// (KParams<T>).
     constexpr bool SC = MODE == kModeScalar;
     static_assert(!SPLIT || (MODE == kModeV2 && !ROOT2), "the sample-parallel kernels cover the live path only");
     // fp64 at 5+ waves per SIMD: a 64-entry queue (half the LDS), so the parked ray fits in 32 KB per
@@ -179,7 +180,14 @@
                     const auto& sq = *cold_split_args<T>();
                     const uint32_t px = item / sq.nsub;
                     first = (item - px * sq.nsub) * sq.S;
-                    cur_end = min(spp, first + sq.S);
+                    if constexpr (WIN) {   // a session's window [s_begin, spp), items on the grid s_base + j S
+                        const auto& wq = *cold_window_args<T>();
+                        first += wq.s_base;
+                        cur_end = min(spp, first + sq.S);
+                        first = max(first, wq.s_begin);
+                    } else {
+                        cur_end = min(spp, first + sq.S);
+                    }
                     item = px;
                 }
                 const uint32_t ri = item / q.col_count, ci = item % q.col_count;

@@ -2,12 +2,17 @@
 //
 //   rt-render [--scene scene.toml] [--width 3840] [--height 2160] [--spp 100] [--bounces 50]
 //             [--seed 0x5EED0001] [--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar]
-//             [--out output.png|.ppm] [--block-size B] [--sample-parallel] [--dump-scene]
+//             [--out output.png|.ppm] [--block-size B] [--sample-parallel] [--progressive n1,n2,...]
+//             [--dump-scene]
 //
 // --mode picks which of the reference's renderers is reproduced (include/rt_mi355x.h): the live
 // render_vectorized2 (default), render_vectorized, or the scalar render.
 // --sample-parallel deals each pixel's samples to several waves where a launch has fewer pixels than the chip
 // has waves (rt_render_split_async's own plan; small frames at a high spp; the live path only, same image).
+// --progressive n1,n2,... renders in one progressive session (rt_progressive_*): after each count (strictly
+// increasing, all below --spp) it writes <out stem>_spp<count, 7 digits><ext> and prints one line with the
+// count, the kernel time so far and the sample rate; only the new samples of a step are traced.  At --spp it
+// writes --out, byte for byte the file the same command writes without --progressive.  The live path only.
 //
 // Defaults are main.rs's hard-coded values (scene.toml in the working directory, 3840x2160, 50
 // bounces, 100 spp, camera from (16,2,18.5) looking at the origin, vfov 30, focal 10, no defocus,
@@ -19,6 +24,7 @@
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "image.hpp"
 #include "scene.hpp"
@@ -71,6 +77,8 @@ int main(int argc, char** argv) {
     uint32_t width = 3840, height = 2160, spp = 100, bounces = 50, flags = 0, block_size = 0;
     uint64_t seed = 0x5EED0001ull;
     bool dump = false, sample_parallel = false;
+    std::string progressive_arg;
+    bool progressive = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -96,13 +104,40 @@ int main(int argc, char** argv) {
         else if (a == "--out") out = next();
         else if (a == "--block-size") block_size = (uint32_t)std::stoul(next());
         else if (a == "--sample-parallel") sample_parallel = true;
+        else if (a == "--progressive") { progressive_arg = next(); progressive = true; }
         else if (a == "--dump-scene") dump = true;
         else if (a == "-h" || a == "--help") {
             std::puts("rt-render [--scene scene.toml] [--width W] [--height H] [--spp S] [--bounces B] [--seed N] "
                       "[--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar] [--out output.png] [--block-size B] "
-                      "[--sample-parallel] [--dump-scene]");
+                      "[--sample-parallel] [--progressive n1,n2,...] [--dump-scene]");
             return 0;
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
+    }
+    std::vector<uint32_t> counts;   // --progressive: the sample counts before --spp
+    if (progressive) {
+        auto bad = [](const std::string& why) {
+            std::fprintf(stderr, "--progressive: %s\n", why.c_str());
+            return 2;
+        };
+        if (flags & RT_FLAG_ROOT2)
+            return bad("not with --root2: a session keeps per-sample records, which only the live path's kernels write "
+                       "(the --root2 kernels reduce a pixel inside the wave)");
+        if (flags & (RT_FLAG_MODE_VECTORIZED | RT_FLAG_MODE_SCALAR | RT_FLAG_MODE_VECTORIZED3))
+            return bad("only with --mode vectorized2: a session keeps per-sample records, which only the live path's "
+                       "kernels write (the other modes reduce a pixel inside the wave)");
+        if (block_size != 0) return bad("not with --block-size: every step is one launch over the whole image");
+        std::stringstream ps(progressive_arg);
+        std::string tok;
+        while (std::getline(ps, tok, ',')) {
+            if (tok.empty() || tok.find_first_not_of("0123456789") != std::string::npos || tok.size() > 9)
+                return bad("'" + tok + "' is not a sample count (expected n1,n2,...)");
+            const uint32_t n = (uint32_t)std::stoul(tok);
+            if (n == 0) return bad("a sample count of 0");
+            if (!counts.empty() && n <= counts.back()) return bad("the counts must be strictly increasing");
+            if (n >= spp) return bad("the counts must be below --spp (" + std::to_string(spp) + "), where --out is written");
+            counts.push_back(n);
+        }
+        if (counts.empty() || progressive_arg.back() == ',') return bad("expected n1,n2,...");
     }
     try {
         std::ifstream in(scene_path, std::ios::binary);   // main.rs:31-34
@@ -130,7 +165,20 @@ int main(int argc, char** argv) {
         GpuRenderer renderer(seed, flags, block_size, sample_parallel);   // block_size 128: TileRenderer::new(None, 128), main.rs:62
         std::fprintf(stderr, "Rendering %u by %u image on %s (%s)...\n", width, height, rt_version(),
                      (flags & RT_FLAG_F32) ? "fp32" : "fp64");
-        auto [image, stat] = renderer.render(bounces, spp, scene, camera);                     // main.rs:64
+        auto step = [&](uint32_t n, const RgbImage& im, const rt_stats& so_far, bool range_err) {
+            const size_t dot = out.find_last_of('.'), slash = out.find_last_of('/');
+            const bool ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+            char tag[32];
+            std::snprintf(tag, sizeof tag, "_spp%07u", n);
+            const std::string path = (ext ? out.substr(0, dot) : out) + tag + (ext ? out.substr(dot) : "");
+            save_image(path, im.width, im.height, im.data.data());
+            std::printf("Progressive: %u spp -> %s, kernel %.3f ms, %.2f Msamples/s%s\n", n, path.c_str(), so_far.kernel_ms,
+                        so_far.kernel_ms > 0 ? (double)so_far.samples / (so_far.kernel_ms * 1e-3) / 1e6 : 0.0,
+                        range_err ? " (a pixel channel exceeded 2.0 at this count)" : "");
+            std::fflush(stdout);
+        };
+        auto [image, stat] = progressive ? renderer.render_progressive(bounces, spp, scene, camera, counts, step)
+                                         : renderer.render(bounces, spp, scene, camera);       // main.rs:64
         save_image(out, image.width, image.height, image.data.data());                         // main.rs:66
         std::printf("Image Size: %u x %u\n", camera.image_width(), camera.image_height());    // main.rs:68-71
         std::printf("Total Pixels: %zu\n", stat.pixels_rendered);

@@ -310,6 +310,62 @@ struct GpuRenderer : Renderer {
         return {std::move(img), stat};
     }
 
+    // Progressive render (rt_progressive_*): one session of capacity spp over the whole image, extended to
+    // each of `counts` (strictly increasing, all below spp) and then to spp, an image at every step; only the
+    // new samples of a step are traced, and every image is the one render() gives at that sample count.
+    // step(count, image, stats so far, range error at this count) is called after each of `counts`.  A channel
+    // above 2.0 at a step is reported, not thrown (at a few samples the reference's own arithmetic gets there);
+    // at spp it panics as render() does.  The live path only (flags: RT_FLAG_F32 or none).
+    template <typename Step>
+    std::pair<RgbImage, RenderStat> render_progressive(size_t max_bounces, size_t spp, const Scene& scene,
+                                                       const Camera& camera, const std::vector<uint32_t>& counts,
+                                                       Step&& step) {
+        const auto t0 = std::chrono::steady_clock::now();
+        FlatScene flat = scene.flatten();
+        rt_scene rs = flat.view();
+        RgbImage img{camera.image_width(), camera.image_height(), {}};
+        const size_t npx = (size_t)img.width * img.height;
+        img.data.resize(npx * 3);
+        struct Ctx {
+            rt_context* c = nullptr;
+            void* buf = nullptr;
+            ~Ctx() { if (buf) rt_device_free(c, buf); if (c) rt_context_destroy(c); }   // destroy ends the session
+        } x;
+        auto chk = [](int rc, const char* what) {
+            if (rc != RT_OK) throw Panic(std::string(what) + ": " + rt_last_error());
+        };
+        chk(rt_context_create(0, &x.c), "rt_context_create");
+        chk(rt_context_set_scene(x.c, &rs), "rt_context_set_scene");
+        chk(rt_device_alloc(x.c, npx * 3, &x.buf), "rt_device_alloc");
+        chk(rt_progressive_begin(x.c, &camera.c, (uint32_t)max_bounces, (uint32_t)spp, seed, flags, nullptr, 0),
+            "rt_progressive_begin");
+        rt_stats total{};
+        auto extend = [&](uint32_t n) -> bool {   // true: RT_ERR_RANGE at this count
+            chk(rt_progressive_extend_async(x.c, n, x.buf, nullptr, nullptr), "rt_progressive_extend_async");
+            rt_stats st{};
+            const int rc = rt_context_collect(x.c, nullptr, &st);
+            if (rc != RT_ERR_RANGE) chk(rc, "rt_context_collect");
+            chk(rt_memcpy_d2h(x.c, img.data.data(), x.buf, npx * 3), "rt_memcpy_d2h");
+            total.kernel_ms += st.kernel_ms;
+            total.pixels = npx;
+            total.samples += st.samples;
+            total.ray_segments += st.ray_segments;
+            total.lane_slots += st.lane_slots;
+            total.bounce_iters += st.bounce_iters;
+            total.kernel_id = st.kernel_id;
+            total.kernel_wg_per_cu = st.kernel_wg_per_cu;
+            return rc == RT_ERR_RANGE;
+        };
+        for (uint32_t n : counts) {
+            const bool range_err = extend(n);
+            step(n, img, total, range_err);
+        }
+        if (extend((uint32_t)spp)) throw Panic("assertion failed: a pixel channel exceeded 2.0 (color.rs:55-57)");
+        chk(rt_progressive_end(x.c), "rt_progressive_end");
+        RenderStat stat(std::chrono::steady_clock::now() - t0, npx, total);
+        return {std::move(img), stat};
+    }
+
   private:
     void render_blocks(const rt_scene& rs, const Camera& camera, uint32_t max_bounces, uint32_t spp, RgbImage& img,
                        rt_stats& total, uint32_t B, bool print_blocks) {

@@ -126,13 +126,15 @@ EXPORTED = [
     "rt_camera_new", "rt_metal_clamp_fuzz", "rt_render", "rt_context_create", "rt_context_destroy",
     "rt_context_set_scene", "rt_render_async", "rt_context_collect", "rt_device_alloc", "rt_device_free",
     "rt_memcpy_d2h", "rt_last_error", "rt_version", "rt_render_split_async", "rt_split_plan",
+    "rt_progressive_bytes", "rt_progressive_begin", "rt_progressive_extend_async", "rt_progressive_end",
 ]
 
 _lib = None
 
 # The sources the Makefile hashes into rt_version() ("src=<hash>"), in its order (SRC, then HDR).
 KERNEL_SOURCES = ["rt_kernel.hip", "rt_experiments.hpp", "rt_common.hpp", "rt_sweep.hpp", "rt_camera.hpp",
-                  "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp"]
+                  "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp",
+                  "rt_progressive_plan.hpp"]
 SOURCE_FILES = [os.path.join(PKG_DIR, "csrc", f) for f in KERNEL_SOURCES] + \
                [os.path.join(os.path.dirname(PKG_DIR), "include", "rt_mi355x.h")]
 
@@ -186,6 +188,10 @@ def load_library(path=None):
     lib.rt_render_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp]
     lib.rt_render_split_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp, u32]
     lib.rt_split_plan.argtypes = [u64, u32, u32, P(u32), P(u64)]
+    lib.rt_progressive_bytes.argtypes = [u64, u32, u32, u32, P(u64)]
+    lib.rt_progressive_begin.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), u64]
+    lib.rt_progressive_extend_async.argtypes = [vp, u32, vp, vp, vp]
+    lib.rt_progressive_end.argtypes = [vp]
     lib.rt_context_collect.argtypes = [vp, vp, P(RtStats)]
     lib.rt_device_alloc.argtypes = [vp, ctypes.c_size_t, P(vp)]
     lib.rt_device_free.argtypes = [vp, vp]

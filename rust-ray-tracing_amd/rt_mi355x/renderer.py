@@ -20,7 +20,9 @@ from . import abi
 class RenderStat:
     """renderer.rs:11-34 (+ the GPU work counters)."""
 
-    def __init__(self, duration, pixels_rendered, kernel_ms=0.0, samples=0, ray_segments=0):
+    def __init__(self, duration, pixels_rendered, kernel_ms=0.0, samples=0, ray_segments=0, range_error=False):
+        # range_error (GpuRenderer.progressive only): a pixel channel exceeded 2.0 at this step (RT_ERR_RANGE)
+        self.range_error = bool(range_error)
         self._duration = float(duration)
         self._pixels = int(pixels_rendered)
         self._pps = self._pixels / self._duration if self._duration > 0 else 0.0
@@ -55,6 +57,96 @@ def split_argument(samples_per_item):
     return samples_per_item
 
 
+def check_schedule(schedule):
+    """A progressive schedule checked before any GPU call: a non-empty, strictly increasing list of positive
+    sample counts.  Returns it as a list of ints."""
+    counts = list(schedule)
+    if not counts:
+        raise ValueError("progressive schedule is empty")
+    for n in counts:
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise ValueError(f"progressive schedule entries must be ints, not {n!r}")
+    counts = [int(n) for n in counts]
+    if counts[0] < 1:
+        raise ValueError(f"progressive schedule must start at 1 sample or more, not {counts[0]}")
+    for a, b in zip(counts, counts[1:]):
+        if b <= a:
+            raise ValueError(f"progressive schedule must be strictly increasing ({a} is followed by {b})")
+    return counts
+
+
+class ProgressiveSession:
+    """One progressive session on a GpuRenderer's context (rt_progressive_*, include/rt_mi355x.h): the
+    samples traced so far stay in a record buffer, extend() adds more and takes an image at any count.  The
+    image after n samples is bit for bit render_flat's at spp = n.  A context manager; close() frees the buffer."""
+
+    def __init__(self, renderer, max_bounces, spp_capacity, flat, cam, tile_range=None, max_bytes=0):
+        self.renderer, self.lib = renderer, renderer.lib
+        self.capacity = int(spp_capacity)
+        self._done = 0
+        self._open = False
+        if renderer._scene_flat is not flat:
+            renderer.set_scene(flat)
+        tr = tile_range if tile_range is not None else abi.RtTileRange(0, 1, cam.image_height, 0, cam.image_width)
+        self.npx = tr.row_count * tr.col_count
+        abi.check(self.lib, self.lib.rt_progressive_begin(renderer.ctx, ctypes.byref(cam), max_bounces, spp_capacity,
+                                                          renderer.seed, renderer.flags, ctypes.byref(tr), max_bytes))
+        self._open = True
+        renderer._session = self
+
+    @property
+    def done(self):
+        """Samples per pixel traced so far."""
+        return self._done
+
+    def extend(self, spp_total, want_linear=False, image=True, stream=None):
+        """Trace samples [done, spp_total) and reduce [0, spp_total): (rgb [n,3] u8, linear [n,3] f64 | None,
+        RtStats, rc) like render_flat; rc is RT_OK or RT_ERR_RANGE.  image=False: trace only, returns the RtStats."""
+        if not self._open:
+            raise RuntimeError("the progressive session is closed")
+        lib, ctx = self.lib, self.renderer.ctx
+        d_rgb, d_lin = ctypes.c_void_p(), ctypes.c_void_p()
+        try:
+            if image:
+                abi.check(lib, lib.rt_device_alloc(ctx, self.npx * 3, ctypes.byref(d_rgb)))
+                if want_linear:
+                    abi.check(lib, lib.rt_device_alloc(ctx, self.npx * 3 * 8, ctypes.byref(d_lin)))
+            abi.check(lib, lib.rt_progressive_extend_async(ctx, spp_total, d_rgb if image else None,
+                                                           d_lin if image and want_linear else None, stream))
+            self._done = spp_total
+            st = abi.RtStats()
+            rc = abi.check(lib, lib.rt_context_collect(ctx, stream, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
+            if not image:
+                return st
+            rgb = np.empty((self.npx, 3), dtype=np.uint8)
+            abi.check(lib, lib.rt_memcpy_d2h(ctx, rgb.ctypes.data, d_rgb, self.npx * 3))
+            lin = None
+            if want_linear:
+                lin = np.empty((self.npx, 3), dtype=np.float64)
+                abi.check(lib, lib.rt_memcpy_d2h(ctx, lin.ctypes.data, d_lin, self.npx * 3 * 8))
+        finally:
+            if d_rgb:
+                lib.rt_device_free(ctx, d_rgb)
+            if d_lin:
+                lib.rt_device_free(ctx, d_lin)
+        return rgb, lin, st, rc
+
+    def close(self):
+        if self._open:
+            self._open = False
+            if self.renderer._session is self:
+                self.renderer._session = None
+            if self.renderer.ctx:   # rt_context_destroy has ended it otherwise
+                abi.check(self.lib, self.lib.rt_progressive_end(self.renderer.ctx))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class GpuRenderer(Renderer):
     """Drop-in for TileRenderer: renders the whole image on one MI355X via rt_render_async.
 
@@ -85,9 +177,13 @@ class GpuRenderer(Renderer):
         self.ctx = ctypes.c_void_p()
         abi.check(self.lib, self.lib.rt_context_create(device, ctypes.byref(self.ctx)))
         self._scene_flat = None   # the FlatScene last uploaded (held, so its identity cannot be reused)
+        self._session = None      # the open ProgressiveSession, if any (one per context)
 
     def close(self):
         if self.ctx:
+            if self._session is not None:   # rt_context_destroy ends it
+                self._session._open = False
+                self._session = None
             self.lib.rt_context_destroy(self.ctx)
             self.ctx = ctypes.c_void_p()
 
@@ -156,3 +252,31 @@ class GpuRenderer(Renderer):
             raise abi.RtError(rc, "a pixel channel exceeded 2.0 (reference: Color::to_u8_array panics)")
         img = rgb.reshape(cam.image_height, cam.image_width, 3)
         return img, RenderStat(dt, cam.image_width * cam.image_height, st.kernel_ms, st.samples, st.ray_segments)
+
+    def begin_progressive(self, max_bounces, spp_capacity, scene, camera, tile_range=None, max_bytes=0):
+        """Open a ProgressiveSession (rt_progressive_begin) for up to spp_capacity samples per pixel.  The live
+        path only: mode "vectorized2" without root2.  max_bytes: the most the record buffer may take
+        (0 = the library's 24 GB budget; see rt_progressive_bytes for the cost)."""
+        flat = scene.flatten() if hasattr(scene, "flatten") else scene
+        cam = camera.abi if hasattr(camera, "abi") else camera
+        return ProgressiveSession(self, max_bounces, spp_capacity, flat, cam, tile_range, max_bytes)
+
+    def progressive(self, max_bounces, schedule, scene, camera):
+        """Render at each sample count of `schedule` (strictly increasing), tracing only the new samples of
+        each step: yields (spp, image HxWx3 uint8, RenderStat) per step, every image equal to render()'s at
+        that spp.  A step whose image has a channel above 2.0 (RT_ERR_RANGE; at 1 spp the reference's own
+        arithmetic gets there) is yielded with stat.range_error set instead of raising, so that a preview
+        never aborts the run.  The stat's samples and ray_segments are those of the step."""
+        counts = check_schedule(schedule)   # before any GPU call
+        return self._progressive(max_bounces, counts, scene, camera)
+
+    def _progressive(self, max_bounces, counts, scene, camera):
+        cam = camera.abi if hasattr(camera, "abi") else camera
+        with self.begin_progressive(max_bounces, counts[-1], scene, cam) as session:
+            for n in counts:
+                t0 = time.perf_counter()
+                rgb, _, st, rc = session.extend(n)
+                dt = time.perf_counter() - t0
+                img = rgb.reshape(cam.image_height, cam.image_width, 3)
+                yield n, img, RenderStat(dt, cam.image_width * cam.image_height, st.kernel_ms, st.samples,
+                                         st.ray_segments, range_error=rc == abi.RT_ERR_RANGE)
