@@ -95,6 +95,47 @@ void oracle_to_u8(const double rgb[3], uint8_t out[3], int* panics) {
     }
 }
 
+/* Batched probes of the functions that hold FMAs or the draw mapping (tests/test_gpu_device_math.py compares the
+ * kernel's device functions with them).  Vectors are component-major: x at [i], y at [n + i], z at [2n + i]. */
+#define ORACLE_PROBES(REAL, sfx)                                                                                  \
+    void oracle_sincos2pi_##sfx##_n(const REAL* u, REAL* s, REAL* c, size_t n) {                                  \
+        for (size_t i = 0; i < n; ++i) sincos2pi_##sfx(u[i], &s[i], &c[i]);                                       \
+    }                                                                                                             \
+    void oracle_unit_vec_##sfx##_n(const REAL* u1, const REAL* u2, REAL* out, size_t n) {                         \
+        for (size_t i = 0; i < n; ++i) {                                                                          \
+            v3_##sfx r = unit_vec_##sfx(u1[i], u2[i]);                                                            \
+            out[i] = r.x; out[n + i] = r.y; out[2 * n + i] = r.z;                                                 \
+        }                                                                                                         \
+    }                                                                                                             \
+    void oracle_unit_##sfx##_n(const REAL* v, REAL* out, size_t n) {                                              \
+        for (size_t i = 0; i < n; ++i) {                                                                          \
+            v3_##sfx r = unit_##sfx(mk_##sfx(v[i], v[n + i], v[2 * n + i]));                                      \
+            out[i] = r.x; out[n + i] = r.y; out[2 * n + i] = r.z;                                                 \
+        }                                                                                                         \
+    }                                                                                                             \
+    void oracle_refract_##sfx##_n(const REAL* v, const REAL* nn, const REAL* ratio, REAL* out, size_t n) {        \
+        for (size_t i = 0; i < n; ++i) {                                                                          \
+            v3_##sfx r = refract_##sfx(mk_##sfx(v[i], v[n + i], v[2 * n + i]),                                    \
+                                       mk_##sfx(nn[i], nn[n + i], nn[2 * n + i]), ratio[i]);                      \
+            out[i] = r.x; out[n + i] = r.y; out[2 * n + i] = r.z;                                                 \
+        }                                                                                                         \
+    }                                                                                                             \
+    void oracle_q8_##sfx##_n(const REAL* v, uint8_t* out, size_t n) {                                             \
+        for (size_t i = 0; i < n; ++i) out[i] = q8_##sfx(v[i]);                                                   \
+    }                                                                                                             \
+    /* draw + u01 / u01b; (k0, k1) = (seed lo, seed hi), the f32 key fold included; r: word w at [w * n + i] */    \
+    void oracle_draw_##sfx##_n(const uint32_t* sid, const uint32_t* pix, const uint32_t* k, const uint32_t* stream, \
+                               uint32_t k0, uint32_t k1, uint32_t* r, REAL* ua, REAL* ub, size_t n) {             \
+        for (size_t i = 0; i < n; ++i) {                                                                          \
+            uint32_t b[4];                                                                                        \
+            draw_##sfx(sid[i], pix[i], k[i], stream[i], k0, k1, b);                                               \
+            for (int w = 0; w < 4; ++w) r[(size_t)w * n + i] = b[w];                                              \
+            ua[i] = u01_##sfx(b); ub[i] = u01b_##sfx(b);                                                          \
+        }                                                                                                         \
+    }
+ORACLE_PROBES(double, f64)
+ORACLE_PROBES(float, f32)
+
 static cam_r_f64 cam_to_r64(const or_camera* cam) {
     cam_r_f64 C;
     C.W = cam->image_width; C.H = cam->image_height;

@@ -103,6 +103,21 @@ void oracle_to_u8(const double rgb[3], uint8_t out[3], int* panics);
 void oracle_get_ray_f64(const or_camera* cam, uint32_t col, uint32_t row, uint32_t sample,
                         uint64_t seed, double origin[3], double dir[3]);
 
+/* Batched probes (sfx = f64 | f32) for the device-math tests: sincos2pi, unit_vec, unit, refract, q8 and
+ * draw + u01 / u01b of n inputs.  Vectors are component-major (x at [i], y at [n + i], z at [2n + i]); draw's
+ * block is word-major (word w at [w * n + i]) and takes (k0, k1) = (seed lo, seed hi). */
+#include <stddef.h>
+#define ORACLE_PROBE_DECLS(REAL, sfx)                                                                             \
+    void oracle_sincos2pi_##sfx##_n(const REAL* u, REAL* s, REAL* c, size_t n);                                   \
+    void oracle_unit_vec_##sfx##_n(const REAL* u1, const REAL* u2, REAL* out, size_t n);                          \
+    void oracle_unit_##sfx##_n(const REAL* v, REAL* out, size_t n);                                               \
+    void oracle_refract_##sfx##_n(const REAL* v, const REAL* nn, const REAL* ratio, REAL* out, size_t n);         \
+    void oracle_q8_##sfx##_n(const REAL* v, uint8_t* out, size_t n);                                              \
+    void oracle_draw_##sfx##_n(const uint32_t* sid, const uint32_t* pix, const uint32_t* k, const uint32_t* stream, \
+                               uint32_t k0, uint32_t k1, uint32_t* r, REAL* ua, REAL* ub, size_t n);
+ORACLE_PROBE_DECLS(double, f64)
+ORACLE_PROBE_DECLS(float, f32)
+
 /* The reference-shaped CPU baseline (packed_avx2.h): the same results as oracle_render_f64, computed
  * the way the reference runs them (4-lane f64 AVX2 packets, 128x128 tiles through a shared queue).
  * rgb_out / lin_out are full-frame (W*H*3); only the listed tiles (row-major tile grid; NULL = all)

@@ -441,7 +441,7 @@ __device__ __forceinline__ void next_ray(bool cam, uint32_t colx, uint32_t rowy,
         const T ratio = front ? m.p[1] : m.p[0];   // 1/ior : ior
         const V3<T> nn = m.hollow ? neg(nrm) : nrm;
         const T ct = fmin(dot(neg(d), nn), T(1.0));
-        const T st = sqrt_nd(T(1.0) - ct * ct);   // ct <= 1: 0, >= 2^-24 or negative
+        const T st = sqrt_nd(T(1.0) - ct * ct);   // ct <= 1: 0, >= 2^-24 or <= -2^-24
         bool refl = ratio * st > T(1.0);
         if (!refl) {   // Dielectric::reflectance (materials.rs:121-124), powi(5) = x*((x*x)*(x*x))
             const T r0 = front ? m.p[2] : m.p[3];   // r0_front : r0_back

@@ -22,9 +22,12 @@ template <typename T> __device__ __forceinline__ V3<T> mul(V3<T> a, T s) { retur
 template <typename T> __device__ __forceinline__ V3<T> dvs(V3<T> a, T s) { return mk(a.x / s, a.y / s, a.z / s); }
 // a / |a| for fp32 (unit(), next_ray's normal): the compiler's correctly rounded division is
 // div_scale x2, rcp, 6 FMAs, div_fmas, div_fixup per component; when v_div_scale would scale nothing and
-// div_fixup has no special case to fix (every lane: 2^-20 <= len <= 2^20 and every |component| >= 2^-100,
-// which bounds |a_i / len| by ~1 since |a_i| <= len), the same sequence without them gives the same bits,
-// with the denominator's refined reciprocal shared by the three components.  Otherwise the full division.
+// div_fixup has no special case to fix (every lane: 2^-20 <= s <= 2^20 and every |component| >= 2^-100), the
+// same sequence without them gives the same bits, with the denominator's refined reciprocal shared by the three
+// components.  Otherwise the full division.  unit() and the packed normal have |a_i| <= s (1 + 2^-22); the scalar
+// mode divides p - c by the radius, where the quotient is bounded only by what a hit can form (< 2^110, DESIGN.md
+// section 2).  Checked on the GPU up to there, next to rounding boundaries and in mixed waves
+// (tests/test_gpu_device_math.py).  A quotient that overflowed would come out NaN, not inf: no caller forms one.
 template <> __device__ __forceinline__ V3<float> dvs(V3<float> a, float s) {
     const float mn = fminf(fminf(fabsf(a.x), fabsf(a.y)), fabsf(a.z));
     const bool ok = s >= 0x1.0p-20f && s <= 0x1.0p20f && mn >= 0x1.0p-100f;
@@ -40,10 +43,12 @@ template <> __device__ __forceinline__ V3<float> dvs(V3<float> a, float s) {
     }
     return mk(a.x / s, a.y / s, a.z / s);
 }
-// sqrt, correctly rounded, of an argument known to be +-0, >= 2^-96, +inf, negative or NaN (never a tiny
-// positive one): v_sqrt_f32 (within 1 ulp) and the compiler's own correction by the residuals of the two
-// neighbours, without its scaling for arguments below 2^-96 and its special-value select (both no-ops
-// here: 0, +inf and NaN come through the correction unchanged).  fp64: the library sqrt.
+// sqrt, correctly rounded, of an argument known to be +-0, >= 2^-96, +inf, <= -2^-96 or NaN (never a tiny
+// nonzero one of either sign): v_sqrt_f32 (within 1 ulp) and the compiler's own correction by the residuals of
+// the two neighbours, without its scaling for arguments below 2^-96 and its special-value select (both no-ops
+// here: 0, +inf and NaN come through the correction unchanged).  The scaling is what makes the library's
+// sqrt of a negative subnormal NaN: v_sqrt_f32 takes a subnormal input as a zero of its sign, so without it
+// sqrt(-subnormal) is -0 (tests/test_gpu_device_math.py, the exhaustive sweep).  fp64: the library sqrt.
 __device__ __forceinline__ float sqrt_nd(float x) {
     const float s = __builtin_amdgcn_sqrtf(x);
     const float sdn = __int_as_float(__float_as_int(s) - 1), sup = __int_as_float(__float_as_int(s) + 1);
@@ -86,12 +91,12 @@ __device__ __forceinline__ double sqrt_len(double x) {
     }
     return sqrt(x);
 }
-// fp32: sqrt_nd when no lane holds a tiny positive argument (a wave ballot), else the library sqrtf -- the same
-// correctly rounded value.  The library sequence is ~16 VALU ops, most of them single-issue (compares, selects,
+// fp32: sqrt_nd when no lane holds a tiny nonzero argument of either sign (a wave ballot), else the library
+// sqrtf -- the same correctly rounded value.  The library sequence is ~16 VALU ops, most of them single-issue (compares, selects,
 // constant operands): unit() of every camera ray, the scatter's normal length and the hit test's sqrt(disc) take
 // the short form (round 6, same-box C fp32 +1.2 %, E +0.4 %: profiles/r06/sqrt_len_nd_ab.txt).
 __device__ __forceinline__ float sqrt_len(float x) {
-    if (__builtin_expect(__ballot(x > 0.0f && x < 0x1.0p-96f) == 0ull, 1)) return sqrt_nd(x);
+    if (__builtin_expect(__ballot(x != 0.0f && fabsf(x) < 0x1.0p-96f) == 0ull, 1)) return sqrt_nd(x);
     return sqrtf(x);
 }
 template <typename T> __device__ __forceinline__ V3<T> neg(V3<T> a) { return mk(-a.x, -a.y, -a.z); }

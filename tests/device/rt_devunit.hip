@@ -1,0 +1,245 @@
+// rt_devunit.hip — TEST INFRASTRUCTURE ONLY: the kernel's device math (csrc/rt_device.hpp, rt_common.hpp,
+// rt_sweep.hpp), one function per map kernel, out[i] = f(in[i]), behind a C ABI (tests/devunit_bind.py,
+// tests/test_gpu_device_math.py).  Built by `make devunit` with the product's flags into
+// lib/librt_devunit.so; the product library never links it and it is not part of the source hash.
+//
+// Launch shape: 256-thread blocks, n a multiple of 256 (the binding pads with in-contract values), no
+// early return: every lane of every wave holds an input the test chose, so the wave ballots inside
+// dvs / sqrt_len see nothing else.  Vectors are component-major: x at [i], y at [n + i], z at [2n + i].
+// Every entry point takes host pointers, allocates, copies, launches, synchronises, copies back, frees,
+// and returns the HIP error as an int (-1: n is no multiple of 256).
+#include "rt_sweep.hpp"
+
+using namespace rt;
+
+namespace {
+
+constexpr unsigned kBlock = 256;
+
+// Device buffers of one call: freed on scope exit, the first HIP error kept.
+struct Dev {
+    std::vector<void*> ptrs;
+    hipError_t err = hipSuccess;
+    void note(hipError_t e) { if (err == hipSuccess && e != hipSuccess) err = e; }
+    template <typename T> T* out(size_t n) {
+        void* d = nullptr;
+        if (err != hipSuccess) return nullptr;
+        note(hipMalloc(&d, (n ? n : 1) * sizeof(T)));
+        if (d) ptrs.push_back(d);
+        return (T*)d;
+    }
+    template <typename T> T* in(const T* h, size_t n) {
+        T* d = out<T>(n);
+        if (d && n) note(hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice));
+        return d;
+    }
+    template <typename T> void back(T* h, const T* d, size_t n) {
+        if (err == hipSuccess && n) note(hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost));
+    }
+    void sync() {
+        if (err != hipSuccess) return;
+        note(hipGetLastError());
+        note(hipDeviceSynchronize());
+    }
+    bool ok() const { return err == hipSuccess; }
+    ~Dev() { for (void* p : ptrs) (void)hipFree(p); }
+};
+
+__device__ __forceinline__ size_t gid() { return (size_t)blockIdx.x * kBlock + threadIdx.x; }
+template <typename T> __device__ __forceinline__ V3<T> ld3(const T* v, size_t n, size_t i) { return mk(v[i], v[n + i], v[2 * n + i]); }
+template <typename T> __device__ __forceinline__ void st3(T* o, size_t n, size_t i, V3<T> r) { o[i] = r.x; o[n + i] = r.y; o[2 * n + i] = r.z; }
+
+template <typename T> __global__ void k_unit(const T* v, T* o, size_t n) { const size_t i = gid(); st3(o, n, i, unit(ld3(v, n, i))); }
+template <typename T> __global__ void k_dvs(const T* v, const T* s, T* o, size_t n) { const size_t i = gid(); st3(o, n, i, dvs(ld3(v, n, i), s[i])); }
+template <typename T> __global__ void k_sqrt_nd(const T* x, T* o, size_t) { const size_t i = gid(); o[i] = sqrt_nd(x[i]); }
+template <typename T> __global__ void k_sqrt_len(const T* x, T* o, size_t) { const size_t i = gid(); o[i] = sqrt_len(x[i]); }
+template <typename T> __global__ void k_sincos(const T* u, T* so, T* co, size_t) {
+    const size_t i = gid();
+    T s, c;
+    sincos2pi(u[i], s, c);
+    so[i] = s; co[i] = c;
+}
+template <typename T> __global__ void k_unit_vec(const T* u1, const T* u2, T* o, size_t n) { const size_t i = gid(); st3(o, n, i, unit_vec(u1[i], u2[i])); }
+template <typename T> __global__ void k_refract(const T* v, const T* nn, const T* ratio, T* o, size_t n) {
+    const size_t i = gid();
+    st3(o, n, i, refract(ld3(v, n, i), ld3(nn, n, i), ratio[i]));
+}
+template <typename T> __global__ void k_q8(const T* v, uint8_t* o, size_t) { const size_t i = gid(); o[i] = q8(v[i]); }
+template <typename T> __global__ void k_div_dim(const T* x, uint32_t W, double r, T* o, size_t) { const size_t i = gid(); o[i] = div_dim(x[i], W, r); }
+template <typename T>
+__global__ void k_rng(const uint32_t* sid, const uint32_t* pix, const uint32_t* k, const uint32_t* stream, uint32_t k0,
+                      uint32_t k1, uint32_t* r, T* ua, T* ub, size_t n) {
+    const size_t i = gid();
+    const U4 b = rng<T>(sid[i], pix[i], k[i], stream[i], k0, k1);
+    r[i] = b.a; r[n + i] = b.b; r[2 * n + i] = b.c; r[3 * n + i] = b.d;
+    ua[i] = u01a(b, T(0)); ub[i] = u01b(b, T(0));
+}
+__global__ void k_philox(const uint32_t* c, const uint32_t* key, uint32_t* r, size_t n) {
+    const size_t i = gid();
+    const U4 b = philox(c[i], c[n + i], c[2 * n + i], c[3 * n + i], key[i], key[n + i]);
+    r[i] = b.a; r[n + i] = b.b; r[2 * n + i] = b.c; r[3 * n + i] = b.d;
+}
+__global__ void k_philox2(const uint32_t* c, const uint32_t* key, uint32_t* r, size_t n) {
+    const size_t i = gid();
+    const U4 b = philox2(c[i], c[n + i], key[i]);
+    r[i] = b.a; r[n + i] = b.b;
+}
+// hit_update folded over the lane's first cnt[i] (<= 8) candidates, slot-major: hb[c * n + i].
+constexpr uint32_t kSlots = 8;
+template <typename T, bool root2, bool SCALAR>
+__global__ void k_hit(const T* hb, const T* disc, const uint32_t* idx, const uint32_t* cnt, const T* a, T* ot, int32_t* oi,
+                      size_t n) {
+    const size_t i = gid();
+    const T aa = a[i];
+    const T inv_a = SCALAR ? T(0) : T(1.0) / aa;   // nearest_hit
+    const uint32_t m = cnt[i];
+    HitBest<T> bh;
+    for (uint32_t c = 0; c < kSlots; ++c)
+        if (c < m) hit_update<T, root2, SCALAR>(hb[c * n + i], disc[c * n + i], idx[c * n + i], aa, inv_a, bh);
+    ot[i] = bh.bt(); oi[i] = bh.bi();
+}
+
+// sqrt over consecutive fp32 bit patterns, compared on the device with (float)sqrt((double)x) (the f64 sqrt is
+// correctly rounded and 53 >= 2 * 24 + 2, so the double rounding is harmless).  A wave holds 64 consecutive
+// patterns.  mode 0: sqrt_len; mode 1: sqrt_len with lane 7 of every odd wave replaced by a tiny positive
+// argument (below 2^-96), so the other 63 lanes take the ballot's library path; mode 2: sqrt_nd (the caller
+// keeps the range inside its contract).
+constexpr uint32_t kFirst = 16;
+__global__ void k_sqrt_sweep(uint32_t start, uint32_t iters, int mode, unsigned long long* count, uint32_t* first) {
+#pragma unroll 1
+    for (uint32_t it = 0; it < iters; ++it) {
+        const uint32_t off = (it * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
+        uint32_t bits = start + off;
+        if (mode == 1 && (off & 127u) == 71u) bits = (bits >> 5) | 1u;   // in (0, 2^-96): below 0x08000000
+        const float x = __uint_as_float(bits);
+        const float got = mode == 2 ? sqrt_nd(x) : sqrt_len(x);
+        const float want = (float)sqrt((double)x);
+        const bool same = (got != got && want != want) || __float_as_uint(got) == __float_as_uint(want);
+        if (!same) {
+            const unsigned long long slot = atomicAdd(count, 1ull);
+            if (slot < kFirst) first[slot] = bits;
+        }
+    }
+}
+
+template <typename F> int run(size_t n, F&& body) {
+    if (n % kBlock != 0) return -1;
+    Dev d;
+    body(d, dim3((unsigned)(n / kBlock)), dim3(kBlock));
+    return (int)d.err;
+}
+
+}  // namespace
+
+#define LAUNCH(kern, ...) do { if (d.ok() && n) { hipLaunchKernelGGL(kern, g, b, 0, 0, __VA_ARGS__); d.sync(); } } while (0)
+
+#define DEVUNIT_FOR(T, sfx)                                                                                            \
+    int du_unit_##sfx(const T* v, T* out, size_t n) {                                                                  \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* dv = d.in(v, 3 * n); T* o = d.out<T>(3 * n);                                                      \
+            LAUNCH(k_unit<T>, dv, o, n); d.back(out, o, 3 * n); });                                                    \
+    }                                                                                                                  \
+    int du_dvs_##sfx(const T* v, const T* s, T* out, size_t n) {                                                       \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* dv = d.in(v, 3 * n); const T* ds = d.in(s, n); T* o = d.out<T>(3 * n);                            \
+            LAUNCH(k_dvs<T>, dv, ds, o, n); d.back(out, o, 3 * n); });                                                 \
+    }                                                                                                                  \
+    int du_sqrt_nd_##sfx(const T* x, T* out, size_t n) {                                                               \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* dx = d.in(x, n); T* o = d.out<T>(n);                                                              \
+            LAUNCH(k_sqrt_nd<T>, dx, o, n); d.back(out, o, n); });                                                     \
+    }                                                                                                                  \
+    int du_sqrt_len_##sfx(const T* x, T* out, size_t n) {                                                              \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* dx = d.in(x, n); T* o = d.out<T>(n);                                                              \
+            LAUNCH(k_sqrt_len<T>, dx, o, n); d.back(out, o, n); });                                                    \
+    }                                                                                                                  \
+    int du_sincos2pi_##sfx(const T* u, T* s, T* c, size_t n) {                                                         \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* du = d.in(u, n); T* ds = d.out<T>(n); T* dc = d.out<T>(n);                                        \
+            LAUNCH(k_sincos<T>, du, ds, dc, n); d.back(s, ds, n); d.back(c, dc, n); });                                \
+    }                                                                                                                  \
+    int du_unit_vec_##sfx(const T* u1, const T* u2, T* out, size_t n) {                                                \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* d1 = d.in(u1, n); const T* d2 = d.in(u2, n); T* o = d.out<T>(3 * n);                              \
+            LAUNCH(k_unit_vec<T>, d1, d2, o, n); d.back(out, o, 3 * n); });                                            \
+    }                                                                                                                  \
+    int du_refract_##sfx(const T* v, const T* nn, const T* ratio, T* out, size_t n) {                                  \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* dv = d.in(v, 3 * n); const T* dn = d.in(nn, 3 * n); const T* dr = d.in(ratio, n);                 \
+            T* o = d.out<T>(3 * n);                                                                                    \
+            LAUNCH(k_refract<T>, dv, dn, dr, o, n); d.back(out, o, 3 * n); });                                         \
+    }                                                                                                                  \
+    int du_q8_##sfx(const T* v, uint8_t* out, size_t n) {                                                              \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* dv = d.in(v, n); uint8_t* o = d.out<uint8_t>(n);                                                  \
+            LAUNCH(k_q8<T>, dv, o, n); d.back(out, o, n); });                                                          \
+    }                                                                                                                  \
+    int du_div_dim_##sfx(const T* x, uint32_t W, double r, T* out, size_t n) {                                         \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* dx = d.in(x, n); T* o = d.out<T>(n);                                                              \
+            LAUNCH(k_div_dim<T>, dx, W, r, o, n); d.back(out, o, n); });                                               \
+    }                                                                                                                  \
+    int du_rng_##sfx(const uint32_t* sid, const uint32_t* pix, const uint32_t* k, const uint32_t* stream, uint32_t k0, \
+                     uint32_t k1, uint32_t* r, T* ua, T* ub, size_t n) {                                               \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const uint32_t* d0 = d.in(sid, n); const uint32_t* d1 = d.in(pix, n); const uint32_t* d2 = d.in(k, n);     \
+            const uint32_t* d3 = d.in(stream, n);                                                                      \
+            uint32_t* dr = d.out<uint32_t>(4 * n); T* da = d.out<T>(n); T* db = d.out<T>(n);                           \
+            LAUNCH(k_rng<T>, d0, d1, d2, d3, k0, k1, dr, da, db, n);                                                   \
+            d.back(r, dr, 4 * n); d.back(ua, da, n); d.back(ub, db, n); });                                            \
+    }                                                                                                                  \
+    /* mode 0: <T,false,false>, 1: <T,true,false>, 2: <T,*,true> (the scalar mode ignores root2) */                    \
+    int du_hit_##sfx(const T* hb, const T* disc, const uint32_t* idx, const uint32_t* cnt, const T* a, int mode,       \
+                     T* t_out, int32_t* i_out, size_t n) {                                                             \
+        if (mode < 0 || mode > 2) return -1;                                                                           \
+        return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
+            const T* dh = d.in(hb, kSlots * n); const T* dd = d.in(disc, kSlots * n);                                  \
+            const uint32_t* di = d.in(idx, kSlots * n); const uint32_t* dc = d.in(cnt, n); const T* da = d.in(a, n);   \
+            T* ot = d.out<T>(n); int32_t* oi = d.out<int32_t>(n);                                                      \
+            if (mode == 0) LAUNCH((k_hit<T, false, false>), dh, dd, di, dc, da, ot, oi, n);                            \
+            else if (mode == 1) LAUNCH((k_hit<T, true, false>), dh, dd, di, dc, da, ot, oi, n);                        \
+            else LAUNCH((k_hit<T, false, true>), dh, dd, di, dc, da, ot, oi, n);                                       \
+            d.back(t_out, ot, n); d.back(i_out, oi, n); });                                                            \
+    }
+
+extern "C" {
+
+DEVUNIT_FOR(float, f32)
+DEVUNIT_FOR(double, f64)
+
+int du_philox4x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out, size_t n) {
+    return run(n, [&](Dev& d, dim3 g, dim3 b) {
+        const uint32_t* dc = d.in(ctr, 4 * n); const uint32_t* dk = d.in(key, 2 * n); uint32_t* o = d.out<uint32_t>(4 * n);
+        LAUNCH(k_philox, dc, dk, o, n); d.back(out, o, 4 * n); });
+}
+int du_philox2x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out, size_t n) {
+    return run(n, [&](Dev& d, dim3 g, dim3 b) {
+        const uint32_t* dc = d.in(ctr, 2 * n); const uint32_t* dk = d.in(key, n); uint32_t* o = d.out<uint32_t>(2 * n);
+        LAUNCH(k_philox2, dc, dk, o, n); d.back(out, o, 2 * n); });
+}
+// The host's fp32 key fold (rt_kernel.hip launch_t): seed lo ^ fmix32(seed hi), with rt_device.hpp's fmix32.
+uint32_t du_fold_key_f32(uint64_t seed) { return (uint32_t)seed ^ fmix32((uint32_t)(seed >> 32)); }
+
+// sqrt over the `count` bit patterns from `start` (wrapping mod 2^32); count a multiple of 256, and of 2^22 when
+// above 2^22.  *mismatches: how many differ from (float)sqrt((double)x); first[16]: the first offenders.
+int du_sqrt_sweep_f32(uint32_t start, uint64_t count, int mode, uint64_t* mismatches, uint32_t* first) {
+    constexpr uint64_t kGrid = 1u << 14;
+    if (count == 0 || count > (1ull << 32) || count % kBlock != 0 || mode < 0 || mode > 2) return -1;
+    const uint64_t blocks = count / kBlock;
+    if (blocks > kGrid && blocks % kGrid != 0) return -1;
+    const unsigned grid = (unsigned)(blocks > kGrid ? kGrid : blocks);
+    const uint32_t iters = (uint32_t)(blocks / grid);
+    Dev d;
+    unsigned long long zero = 0;
+    uint32_t none[kFirst] = {0};
+    unsigned long long* dc = d.in(&zero, 1);
+    uint32_t* df = d.in(none, kFirst);
+    if (d.ok()) { hipLaunchKernelGGL(k_sqrt_sweep, dim3(grid), dim3(kBlock), 0, 0, start, iters, mode, dc, df); d.sync(); }
+    d.back(&zero, dc, 1);
+    d.back(first, df, kFirst);
+    *mismatches = zero;
+    return (int)d.err;
+}
+
+}  // extern "C"

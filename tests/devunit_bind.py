@@ -1,0 +1,191 @@
+"""ctypes binding of the test-only device library (tests/device/rt_devunit.hip ->
+rust-ray-tracing_amd/lib/librt_devunit.so): the kernel's device math, one function per map kernel.
+
+Every array is padded to a multiple of 256 (whole waves, whole blocks) with a value inside the function's
+fast-path contract, so the wave ballots inside dvs / sqrt_len see only inputs the caller chose; pad() is the
+same padding, for the CPU tests that check the contract per wave.  Vectors are [3, n], component-major.
+RT_DEVUNIT_LIB names another build (the mutation check).
+"""
+import ctypes
+import os
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "rust-ray-tracing_amd")
+DEVUNIT_PATH = os.path.join(PKG, "lib", "librt_devunit.so")
+BLOCK = 256
+WAVE = 64
+SLOTS = 8
+
+_lib = None
+
+
+def load_devunit():
+    global _lib
+    if _lib is not None:
+        return _lib
+    path = os.environ.get("RT_DEVUNIT_LIB", DEVUNIT_PATH)
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: build it with `make -C {PKG} devunit`")
+    lib = ctypes.CDLL(path)
+    vp, sz, u32, u64, f64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_double
+    for sfx in ("f32", "f64"):
+        for name, args in (("unit", [vp, vp, sz]), ("dvs", [vp, vp, vp, sz]), ("sqrt_nd", [vp, vp, sz]),
+                           ("sqrt_len", [vp, vp, sz]), ("sincos2pi", [vp, vp, vp, sz]), ("unit_vec", [vp, vp, vp, sz]),
+                           ("refract", [vp, vp, vp, vp, sz]), ("q8", [vp, vp, sz]), ("div_dim", [vp, u32, f64, vp, sz]),
+                           ("rng", [vp, vp, vp, vp, u32, u32, vp, vp, vp, sz]),
+                           ("hit", [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, sz])):
+            fn = getattr(lib, f"du_{name}_{sfx}")
+            fn.argtypes, fn.restype = args, ctypes.c_int
+    lib.du_philox4x32_10.argtypes = lib.du_philox2x32_10.argtypes = [vp, vp, vp, sz]
+    lib.du_fold_key_f32.argtypes, lib.du_fold_key_f32.restype = [u64], u32
+    lib.du_sqrt_sweep_f32.argtypes = [u32, u64, ctypes.c_int, ctypes.POINTER(u64), vp]
+    _lib = lib
+    return lib
+
+
+def pad(a, fill):
+    """a ([n] or [k, n]) padded along the last axis to a multiple of BLOCK with `fill`, contiguous."""
+    a = np.asarray(a)
+    n = a.shape[-1]
+    m = -(-n // BLOCK) * BLOCK
+    out = np.full(a.shape[:-1] + (m,), fill, dtype=a.dtype)
+    out[..., :n] = a
+    return out
+
+
+def _sfx(dtype):
+    return {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}[np.dtype(dtype)]
+
+
+def _call(name, dtype, *args):
+    rc = getattr(load_devunit(), f"du_{name}_{_sfx(dtype)}" if dtype is not None else f"du_{name}")(*args)
+    if rc != 0:
+        raise RuntimeError(f"du_{name}: HIP error {rc}")
+
+
+def _p(a):
+    return a.ctypes.data
+
+
+def unit(v):
+    n, vp = v.shape[1], pad(v, 1.0)
+    out = np.empty_like(vp)
+    _call("unit", v.dtype, _p(vp), _p(out), vp.shape[1])
+    return out[:, :n]
+
+
+def dvs(v, s):
+    n, vp, sp = v.shape[1], pad(v, 1.0), pad(s, 1.0)
+    out = np.empty_like(vp)
+    _call("dvs", v.dtype, _p(vp), _p(sp), _p(out), vp.shape[1])
+    return out[:, :n]
+
+
+def _map1(name, x, fill=1.0, out_dtype=None):
+    n, xp = x.size, pad(x, fill)
+    out = np.empty(xp.size, out_dtype or x.dtype)
+    _call(name, x.dtype, _p(xp), _p(out), xp.size)
+    return out[:n]
+
+
+def sqrt_nd(x):
+    return _map1("sqrt_nd", x)
+
+
+def sqrt_len(x):
+    return _map1("sqrt_len", x)
+
+
+def q8(v):
+    return _map1("q8", v, out_dtype=np.uint8)
+
+
+def sincos2pi(u):
+    n, up = u.size, pad(u, 0.25)
+    s, c = np.empty_like(up), np.empty_like(up)
+    _call("sincos2pi", u.dtype, _p(up), _p(s), _p(c), up.size)
+    return s[:n], c[:n]
+
+
+def unit_vec(u1, u2):
+    n, a, b = u1.size, pad(u1, 0.25), pad(u2, 0.25)
+    out = np.empty((3, a.size), u1.dtype)
+    _call("unit_vec", u1.dtype, _p(a), _p(b), _p(out), a.size)
+    return out[:, :n]
+
+
+def refract(v, nrm, ratio):
+    n, a, b, r = v.shape[1], pad(v, 1.0), pad(nrm, 1.0), pad(ratio, 1.0)
+    out = np.empty_like(a)
+    _call("refract", v.dtype, _p(a), _p(b), _p(r), _p(out), a.shape[1])
+    return out[:, :n]
+
+
+def div_dim(x, W, r):
+    n, xp = x.size, pad(x, 0.0)
+    out = np.empty_like(xp)
+    _call("div_dim", x.dtype, _p(xp), int(W), float(r), _p(out), xp.size)
+    return out[:n]
+
+
+def fold_key_f32(seed):
+    return int(load_devunit().du_fold_key_f32(seed))
+
+
+def rng(dtype, sid, pix, k, stream, seed):
+    """rng<T> + u01a / u01b with the key the host derives from the 64-bit seed (fp32: folded).
+    Returns (block [4, n] u32, ua, ub); fp32 fills block rows 2, 3 with zero."""
+    n = len(sid)
+    a = [pad(np.asarray(x, np.uint32), 0) for x in (sid, pix, k, stream)]
+    m = a[0].size
+    r, ua, ub = np.empty((4, m), np.uint32), np.empty(m, dtype), np.empty(m, dtype)
+    if np.dtype(dtype) == np.float32:
+        k0, k1 = fold_key_f32(seed), 0
+    else:
+        k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    _call("rng", dtype, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), k0, k1, _p(r), _p(ua), _p(ub), m)
+    return r[:, :n], ua[:n], ub[:n]
+
+
+def philox4x32_10(ctr, key):
+    """ctr [4, n], key [2, n] -> [4, n]."""
+    n, c, k = ctr.shape[1], pad(np.asarray(ctr, np.uint32), 0), pad(np.asarray(key, np.uint32), 0)
+    out = np.empty_like(c)
+    _call("philox4x32_10", None, _p(c), _p(k), _p(out), c.shape[1])
+    return out[:, :n]
+
+
+def philox2x32_10(ctr, key):
+    """ctr [2, n], key [n] -> [2, n]."""
+    n, c, k = ctr.shape[1], pad(np.asarray(ctr, np.uint32), 0), pad(np.asarray(key, np.uint32), 0)
+    out = np.empty_like(c)
+    _call("philox2x32_10", None, _p(c), _p(k), _p(out), c.shape[1])
+    return out[:, :n]
+
+
+HIT_MODES = {"packed": 0, "root2": 1, "scalar": 2}
+
+
+def hit(hb, disc, idx, cnt, a, mode):
+    """hit_update<T, root2, SCALAR> folded over each lane's first cnt (<= 8) candidates (hb, disc, idx: [8, n]).
+    Returns (bt [n], bi [n] int32).  Padding lanes hold no candidate."""
+    n = hb.shape[1]
+    h, d, a_ = pad(hb, 1.0), pad(disc, 1.0), pad(a, 1.0)
+    i, c = pad(np.asarray(idx, np.uint32), 0), pad(np.asarray(cnt, np.uint32), 0)
+    t, bi = np.empty(h.shape[1], hb.dtype), np.empty(h.shape[1], np.int32)
+    _call("hit", hb.dtype, _p(h), _p(d), _p(i), _p(c), _p(a_), HIT_MODES[mode], _p(t), _p(bi), h.shape[1])
+    return t[:n], bi[:n]
+
+
+def sqrt_sweep_f32(start, count, mode):
+    """sqrt over `count` consecutive fp32 bit patterns from `start`, compared on the device with (float)sqrt((double)x).
+    mode 0: sqrt_len; 1: sqrt_len, lane 7 of every odd wave replaced by a tiny positive argument; 2: sqrt_nd.
+    Returns (mismatches, the first up to 16 offending bit patterns)."""
+    mis = ctypes.c_uint64(0)
+    first = np.zeros(16, np.uint32)
+    rc = load_devunit().du_sqrt_sweep_f32(start, count, mode, ctypes.byref(mis), _p(first))
+    if rc != 0:
+        raise RuntimeError(f"du_sqrt_sweep_f32: HIP error {rc}")
+    return mis.value, first[:min(mis.value, 16)]

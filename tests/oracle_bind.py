@@ -42,8 +42,78 @@ def load_oracle(path=None):
     lib.oracle_sincos2pi_f64.argtypes = [f64, ctypes.POINTER(f64), ctypes.POINTER(f64)]
     lib.oracle_to_u8.argtypes = [ctypes.POINTER(f64), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int)]
     lib.oracle_get_ray_f64.argtypes = [vp, u32, u32, u32, u64, ctypes.POINTER(f64), ctypes.POINTER(f64)]
+    sz = ctypes.c_size_t
+    for sfx in ("f64", "f32"):
+        getattr(lib, f"oracle_sincos2pi_{sfx}_n").argtypes = [vp, vp, vp, sz]
+        getattr(lib, f"oracle_unit_vec_{sfx}_n").argtypes = [vp, vp, vp, sz]
+        getattr(lib, f"oracle_unit_{sfx}_n").argtypes = [vp, vp, sz]
+        getattr(lib, f"oracle_refract_{sfx}_n").argtypes = [vp, vp, vp, vp, sz]
+        getattr(lib, f"oracle_q8_{sfx}_n").argtypes = [vp, vp, sz]
+        getattr(lib, f"oracle_draw_{sfx}_n").argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, sz]
+        for name in ("sincos2pi", "unit_vec", "unit", "refract", "q8", "draw"):
+            getattr(lib, f"oracle_{name}_{sfx}_n").restype = None
+    lib.oracle_fmix32.argtypes = [u32]
+    lib.oracle_fmix32.restype = u32
     _libs[path] = lib
     return lib
+
+
+# ---- batched probes (oracle.h ORACLE_PROBE_DECLS): numpy in, numpy out; dtype float32 or float64 picks the build ----
+def _sfx(dtype):
+    return {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}[np.dtype(dtype)]
+
+
+def _c(a, dtype):
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def oracle_sincos2pi(u):
+    u = _c(u, u.dtype)
+    s, c = np.empty_like(u), np.empty_like(u)
+    getattr(load_oracle(), f"oracle_sincos2pi_{_sfx(u.dtype)}_n")(u.ctypes.data, s.ctypes.data, c.ctypes.data, u.size)
+    return s, c
+
+
+def oracle_unit_vec(u1, u2):
+    u1, u2 = _c(u1, u1.dtype), _c(u2, u1.dtype)
+    out = np.empty((3, u1.size), u1.dtype)
+    getattr(load_oracle(), f"oracle_unit_vec_{_sfx(u1.dtype)}_n")(u1.ctypes.data, u2.ctypes.data, out.ctypes.data, u1.size)
+    return out
+
+
+def oracle_unit(v):
+    """v: [3, n] component-major."""
+    v = _c(v, v.dtype)
+    out = np.empty_like(v)
+    getattr(load_oracle(), f"oracle_unit_{_sfx(v.dtype)}_n")(v.ctypes.data, out.ctypes.data, v.shape[1])
+    return out
+
+
+def oracle_refract(v, n, ratio):
+    v, n, ratio = _c(v, v.dtype), _c(n, v.dtype), _c(ratio, v.dtype)
+    out = np.empty_like(v)
+    getattr(load_oracle(), f"oracle_refract_{_sfx(v.dtype)}_n")(v.ctypes.data, n.ctypes.data, ratio.ctypes.data,
+                                                                 out.ctypes.data, v.shape[1])
+    return out
+
+
+def oracle_q8(v):
+    v = _c(v, v.dtype)
+    out = np.empty(v.size, np.uint8)
+    getattr(load_oracle(), f"oracle_q8_{_sfx(v.dtype)}_n")(v.ctypes.data, out.ctypes.data, v.size)
+    return out
+
+
+def oracle_draw(dtype, sid, pix, k, stream, seed):
+    """draw + u01 / u01b for the 64-bit seed: (block [4, n] u32, ua, ub)."""
+    sid, pix, k, stream = (_c(a, np.uint32) for a in (sid, pix, k, stream))
+    n = sid.size
+    r = np.empty((4, n), np.uint32)
+    ua, ub = np.empty(n, dtype), np.empty(n, dtype)
+    getattr(load_oracle(), f"oracle_draw_{_sfx(dtype)}_n")(sid.ctypes.data, pix.ctypes.data, k.ctypes.data, stream.ctypes.data,
+                                                            seed & 0xFFFFFFFF, seed >> 32, r.ctypes.data, ua.ctypes.data,
+                                                            ub.ctypes.data, n)
+    return r, ua, ub
 
 
 def oracle_render(flat, cam, max_bounces, spp, seed, flags=0, pixels=None, precision="f64", threads=None,
