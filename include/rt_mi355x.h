@@ -97,7 +97,9 @@ typedef struct rt_stats {
      *   box_groups          general sweep, 4 boxes each: 18 v_pk_fma_f32 = 72 fp32 FLOP per lane
      *   filter_groups       general sweep, 4 spheres each: 14 v_pk_fma_f32 = 56 fp32 FLOP per lane
      *   exact_tests         general sweep, one sphere each through Sphere::hit_packed's test
-     *                       (objects.rs:252-257): 17 FLOP per lane in the render's precision
+     *                       (objects.rs:252-257): 17 FLOP per lane in the render's precision.  Behind
+     *                       the sphere filter the fp32 non-mega kernels count one per step in which
+     *                       each lane tests one of its own candidates (a different sphere per lane)
      *   cone_tests          camera sweep, 64 cone records each: 23 fp32 FLOP per lane
      *   camera_exact_tests  camera sweep, one sphere each from the camera-origin table: 8 FLOP per
      *                       lane in the render's precision */

@@ -181,7 +181,8 @@ constexpr double kExactRatio = 8.0;  // spheres with |c|_1 + r > kExactRatio x t
 enum WorkCounter : uint32_t {
     kWBox = 0,      // general sweep: box groups tested (4 boxes, 18 v_pk_fma_f32)
     kWFilt = 1,     // general sweep: filter groups tested (4 spheres, 14 v_pk_fma_f32)
-    kWExact = 2,    // general sweep: spheres through the reference's exact test (17 FLOP in T each)
+    kWExact = 2,    // general sweep: spheres through the reference's exact test (17 FLOP in T each); a per-lane
+                    // step (nearest_hit's flush: each lane one sphere of its own) counts one
     kWCone = 3,     // camera sweep: cone tests (64 records per wave test, 23 fp32 FLOP)
     kWCExact = 4,   // camera sweep: exact tests from the camera-origin table (8 FLOP in T each)
     kNWork = 5,

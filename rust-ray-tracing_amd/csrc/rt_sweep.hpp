@@ -13,13 +13,12 @@ namespace rt {
 // pair, K0 = {e1x, e1z}, K1 = {e2x, e2y}, K2 = {e2z, -}, K3 = {-oe1, -oe2}, and each use
 // broadcasts one half with op_sel / op_sel_hi (the compiler materialises such splats as extra VGPR
 // pairs).  The two pairs are interleaved so that no packed result is read by the next instruction
-// (the one-wait-state packed-FP32 read hazard the compiler pads with s_nop).  14 packed ops, then
-// v_and3 + v_bitop3 on the sign bits.
-__device__ __forceinline__ uint32_t filter_group(const SphGroup<float>& cur, f2 K0, f2 K1, f2 K2, f2 K3, uint32_t& s0,
-                                                 uint32_t& s1, f2* D = nullptr) {
+// (the one-wait-state packed-FP32 read hazard the compiler pads with s_nop).  14 packed ops; the
+// result is the four D, r0 = spheres 0, 1 and r1 = spheres 2, 3 (sign set: the sphere cannot be hit).
+__device__ __forceinline__ void filter_group(const SphGroup<float>& cur, f2 K0, f2 K1, f2 K2, f2 K3, f2& r0, f2& r1) {
     const f2 cx0 = {cur.v[0], cur.v[1]}, cy0 = {cur.v[2], cur.v[3]}, cz0 = {cur.v[4], cur.v[5]}, rr0 = {cur.v[6], cur.v[7]};
     const f2 cx1 = {cur.v[8], cur.v[9]}, cy1 = {cur.v[10], cur.v[11]}, cz1 = {cur.v[12], cur.v[13]}, rr1 = {cur.v[14], cur.v[15]};
-    f2 a0, b0, a1, b1, r0, r1;
+    f2 a0, b0, a1, b1;
     asm volatile(
         "v_pk_fma_f32 %[a0], %[cz0], %[K0], %[K3] op_sel:[0,1,0] op_sel_hi:[1,1,0]\n\t"   // cz*e1z - oe1
         "v_pk_fma_f32 %[b0], %[cz0], %[K2], %[K3] op_sel:[0,0,1] op_sel_hi:[1,0,1]\n\t"   // cz*e2z - oe2
@@ -38,12 +37,6 @@ __device__ __forceinline__ uint32_t filter_group(const SphGroup<float>& cur, f2 
         : [a0] "=&v"(a0), [b0] "=&v"(b0), [a1] "=&v"(a1), [b1] "=&v"(b1), [r0] "=&v"(r0), [r1] "=&v"(r1)
         : [cx0] "s"(cx0), [cy0] "s"(cy0), [cz0] "s"(cz0), [rr0] "s"(rr0), [cx1] "s"(cx1), [cy1] "s"(cy1),
           [cz1] "s"(cz1), [rr1] "s"(rr1), [K0] "v"(K0), [K1] "v"(K1), [K2] "v"(K2), [K3] "v"(K3));
-    // ~(D0 & D1 & D2 & D3): sign set iff some sphere of the group passes (D >= +0); s0, s1: the
-    // same per sphere pair, un-negated (sign clear iff a sphere of the pair passes)
-    s0 = __float_as_uint(r0.x) & __float_as_uint(r0.y);
-    s1 = __float_as_uint(r1.x) & __float_as_uint(r1.y);
-    if (D) { D[0] = r0; D[1] = r1; }   // per sphere (fp64 rays: exact tests per sphere)
-    return ~(s0 & s1);
 }
 
 // The camera-batch filter for one 4-sphere group (nearest_hit, CAMT under Q1): per sphere pair
@@ -359,8 +352,9 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
         // 1/sqrt(1 + m/r2min) (r2min: the smallest filtered r2f): the test x'^2 + y'^2 <= r2f is then
         // x^2 + y^2 <= r2f (1 + m/r2min) >= r2f + m.  Per sphere pair: x 2 packed FMAs, y 3,
         // D = r2f - y^2 - x^2 2 -- 7 ops against the exact test's 12.  So every sphere the reference
-        // could hit passes; a group with any passing sphere recomputes all four exactly from the
-        // exact stream, and only the exact values ever reach hit().
+        // could hit passes; a passing sphere is recomputed exactly (fp32 scene-frame kernels: by the lanes
+        // it passes for, `flush` below; fp64 rays and the mega kernels: by the whole wave, exact4), and
+        // only the exact values ever reach hit().
         // Spheres far outside the scene (|c|_1 + r > 8x the median, e.g. a ground sphere) would
         // inflate the margin for all: the host gives them r2f = +inf, "always exact".  Lanes whose
         // basis degenerates (d nearly parallel to y) or whose origin is huge get a zero basis, so
@@ -511,43 +505,6 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
                     if (((pairs >> j) & 1u) && cand_f(hb[j], disc[j])) hit(hb[j], disc[j], sv[j]);
             }
         };
-        // fp32, scene-frame filter groups (not MEGA): the exact test of a taken group takes the centres
-        // from its filter group, already in SGPRs (the same fp32 values, pack_filter / pack_sweep), and
-        // loads only the group's r² and scene indices: one s_load_dwordx8 from its record, which follows the
-        // cluster's filter groups in the same stream (round 6: a separate table behind a kernel-argument load
-        // cost two dependent scalar round trips per taken group; C fp32 +1.1 %, profiles/r06/xrec_inline_ab.txt)
-        auto exact4f = [&](const SphGroup<float>& cur, cptr<float> recp, uint32_t pairs) {
-            KSTAT(0);
-            if constexpr (sizeof(T) == 4) {
-                cptr<uint32_t> xr = (cptr<uint32_t>)recp;
-                uint32_t rec[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) rec[j] = xr[(uint32_t)j];
-                const f2 ox = {o.x, o.x}, oy = {o.y, o.y}, oz = {o.z, o.z};
-                const f2 dx = {d.x, d.x}, dy = {d.y, d.y}, dz = {d.z, d.z};
-                const f2 na = {-a, -a};
-#pragma unroll
-                for (uint32_t q = 0; q < 2; ++q) {
-                    if (!((pairs >> q) & 1u)) continue;
-                    f2 hb, disc;
-                    const float* v = &cur.v[8 * q];
-                    const f2 cx = {v[0], v[1]}, cy = {v[2], v[3]}, cz = {v[4], v[5]};
-                    const f2 r2 = {__uint_as_float(rec[2 * q]), __uint_as_float(rec[2 * q + 1])};
-                    const f2 ocx = ox - cx, ocy = oy - cy, ocz = oz - cz;             // :252
-                    if constexpr (SCALAR) {                                           // objects.rs:217-222
-                        hb = (ocx * dx + ocy * dy) + ocz * dz;
-                        const f2 c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - r2;
-                        disc = hb * hb - (-na) * c;
-                    } else {
-                        hb = fma2(ocz, dz, fma2(ocy, dy, ocx * dx));                  // :255
-                        const f2 c = fma2(ocz, ocz, fma2(ocy, ocy, ocx * ocx)) - r2;  // :256
-                        disc = fma2(hb, hb, na * c);                                  // :257
-                    }
-                    if (cand_f(hb.x, disc.x)) hit(hb.x, disc.x, rec[4 + 2 * q]);
-                    if (cand_f(hb.y, disc.y)) hit(hb.y, disc.y, rec[5 + 2 * q]);
-                }
-            }
-        };
         // Two levels (build_layout): the always-exact spheres first, then spatial clusters of 16
         // spheres (4 groups each) with bounding spheres, 4 bounds per top group.  Per chunk of 32
         // clusters: phase 1 tests the bounds with the lanes' filter (a cluster bound contains its
@@ -557,6 +514,54 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
         const uint32_t nxg = qa.n_xg, ntop = qa.n_top;
         // executed-work counts of this sweep (wave-uniform; work_add below)
         uint32_t n_box = 0, n_filt = 0, n_exact = 0;
+        // fp32, scene-frame filter groups (not MEGA): the exact tests behind the filter run per lane.  The
+        // filter leaves each lane a 16-bit mask of its own passing spheres per walked cluster (bit 15 - s:
+        // slot s), two clusters to a word; after the walked clusters of a super every lane with a bit set
+        // takes one of its spheres per step, gathers that slot's record from its cluster's block of the
+        // filter stream (centres in groups 0..3, the same fp32 values as the exact stream's, pack_filter /
+        // pack_sweep; r^2 and the scene index in the records behind them, inline_stream) and runs the
+        // reference's test for that one sphere (objects.rs:252-257; SCALAR: :217-222).  The wave takes as
+        // many steps as its busiest lane has candidates, not one pair-step per sphere pair that any lane
+        // passes.  The nearest hit does not depend on the visiting order (hit_update), and the super's
+        // cluster boxes were all tested before its first cluster was walked, so nothing waits for these
+        // hits before the next super's box test.  Every slot of a walked cluster lies inside its block,
+        // dummies too (their filter D is -inf: never a candidate).
+        // blk: the block of the even cluster of the pair; cand: bits 0..15 that cluster, 16..31 the next.
+        auto flush = [&](cptr<float> blk, uint32_t cand) {
+            if constexpr (sizeof(T) == 4) {
+                while (__ballot(cand != 0u) != 0ull) {
+                    KSTAT(0);
+                    ++n_exact;
+                    if (cand != 0u) {
+                        const uint32_t b = (uint32_t)__builtin_ctz(cand);
+                        cand &= cand - 1u;
+                        const uint32_t s = (b & 15u) ^ 15u;    // the slot in its cluster
+                        const uint32_t cb = (b & 16u) * 6u;    // the odd cluster's block: 96 words on
+                        // group s / 4, pair (s / 2) % 2, half s % 2: the centre at 16 g + 8 q + h (+ 0, 2, 4),
+                        // r^2 at 64 + 8 g + 2 q + h, the scene index 4 words behind it
+                        const uint32_t ic = cb + (((s & 14u) << 2) | (s & 1u));
+                        const uint32_t ir = cb + (((s & 12u) << 1) | (s & 3u));
+                        const float cx = blk[ic], cy = blk[ic + 2u], cz = blk[ic + 4u], r2 = blk[64u + ir];
+                        uint32_t si = ((cptr<uint32_t>)blk)[68u + ir];
+                        const float ocx = o.x - cx, ocy = o.y - cy, ocz = o.z - cz;   // :252
+                        float hb, disc;
+                        if constexpr (SCALAR) {                                       // objects.rs:217-222
+                            hb = (ocx * d.x + ocy * d.y) + ocz * d.z;
+                            const float c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - r2;
+                            disc = hb * hb - a * c;
+                        } else {
+                            hb = __builtin_fmaf(ocz, d.z, __builtin_fmaf(ocy, d.y, ocx * d.x));              // :255
+                            const float c = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, ocx * ocx)) - r2;   // :256
+                            disc = __builtin_fmaf(hb, hb, -a * c);                                           // :257
+                        }
+                        // the index load stays with the others (sunk into the branch it would be a second
+                        // dependent round trip per step)
+                        asm volatile("" : "+v"(si));
+                        if (cand_f(hb, disc)) hit(hb, disc, si);
+                    }
+                }
+            }
+        };
         // the always-exact groups; fp32 skips a pair of dummies at the end (the ground sphere's group
         // at config C: ground + 3 dummies); in fp64 the variable pair mask costs VGPR spills at W4
         for (uint32_t g = 0; g < nxg; ++g) {
@@ -580,8 +585,10 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
                 mask = lmask(load_lbox((cptr<float>)__builtin_assume_aligned(qa.lclb, 64), sup));
             }
             else mask = box_mask(load_box(ft, sup), B0, B1, B2, B3, B4, btf());
+            uint32_t c01 = 0u, c23 = 0u;   // kInl: the lane's candidates in clusters 0, 1 and 2, 3 of the super
             while (mask != 0u) {
-                const uint32_t kc = 4u * sup + (uint32_t)__builtin_ctz(mask);   // cluster
+                const uint32_t kj = (uint32_t)__builtin_ctz(mask);
+                const uint32_t kc = 4u * sup + kj;   // cluster
                 const uint32_t g0 = nxg + 4u * kc;
                 mask &= mask - 1u;
                 KSTAT(4);
@@ -621,12 +628,25 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
                 // scene-frame stream, the scene indices), then (mega streams) the frame record (inline_stream)
                 constexpr bool kInl = sizeof(T) == 4 && !MEGA && !CAMT;
                 const cptr<float> fgb = MEGA ? fg : ff + 16u * nxg + 96u * kc;
+                uint32_t fm = 0xFFFFu;   // kInl: the lane's rejected slots of this cluster, shifted in from bit 0
                 sphere_loop(fgb, 4u, [&](const SphGroup<float>& cur, uint32_t g) {
-                    uint32_t s0, s1;
-                    // A wave-uniform branch: lanes the filter rejects run the exact test too, and it
-                    // rejects them as well (the filter passes every sphere the reference can hit).
                     f2 Dv[2];
-                    const unsigned long long fpass = __ballot(is_cand(filter_group(cur, L0, L1, L2, L3, s0, s1, sizeof(T) == 8 ? Dv : nullptr)));
+                    filter_group(cur, L0, L1, L2, L3, Dv[0], Dv[1]);
+                    if constexpr (kInl) {
+                        // one v_alignbit_b32 per sphere: fm = fm << 1 | sign(D).  A set sign is "cannot hit"
+                        // (a NaN or +0 D passes, a -inf dummy never does); after 16 spheres slot s is bit 15 - s
+                        fm = __builtin_amdgcn_alignbit(fm, __float_as_uint(Dv[0].x), 31u);
+                        fm = __builtin_amdgcn_alignbit(fm, __float_as_uint(Dv[0].y), 31u);
+                        fm = __builtin_amdgcn_alignbit(fm, __float_as_uint(Dv[1].x), 31u);
+                        fm = __builtin_amdgcn_alignbit(fm, __float_as_uint(Dv[1].y), 31u);
+                        return;
+                    }
+                    // fp64 rays and the mega kernels.  A wave-uniform branch: lanes the filter rejects run
+                    // the exact test too, and it rejects them as well (the filter passes every sphere the
+                    // reference can hit).  s0, s1: sign clear iff a sphere of the pair passes (D >= +0)
+                    const uint32_t s0 = __float_as_uint(Dv[0].x) & __float_as_uint(Dv[0].y);
+                    const uint32_t s1 = __float_as_uint(Dv[1].x) & __float_as_uint(Dv[1].y);
+                    const unsigned long long fpass = __ballot(is_cand(~(s0 & s1)));
                     KSTAT(7, (uint32_t)__popcll(fpass));   // lanes with a candidate in this group
                     if (fpass != 0ull) {
                         // only the sphere pairs some lane passes (one compare each, taken groups
@@ -642,11 +662,19 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
                                     (__ballot(ps(Dv[1].x)) != 0ull ? 4u : 0u) | (__ballot(ps(Dv[1].y)) != 0ull ? 8u : 0u);
                             n_exact += (uint32_t)__builtin_popcount(pairs);
                         }
-                        if constexpr (kInl) exact4f(cur, fgb + 64u + 8u * g, pairs);
-                        else
-                            exact4(g0 + g, pairs, fgb + 68u + 8u * g);
+                        exact4(g0 + g, pairs, fgb + 68u + 8u * g);
                     }
                 });
+                if constexpr (kInl) {
+                    if (kj < 2u) c01 |= ~fm << (16u * kj);
+                    else c23 |= ~fm << (16u * kj - 32u);
+                }
+            }
+            if constexpr (sizeof(T) == 4 && !MEGA) {
+                KSTAT(7, (uint32_t)__popcll(__ballot((c01 | c23) != 0u)));   // lanes with a candidate in this super
+                const cptr<float> sb = ff + 16u * nxg + 384u * sup;
+                flush(sb, c01);
+                flush(sb + 192u, c23);
             }
         };
         // The top level is the super boxes, or (MEGA: scenes with more than 8 super groups, config E)
