@@ -541,7 +541,7 @@ __global__ void build_cam_table(const T* sph, T* cam, uint32_t n_slots, float* c
     }
     if (i < n_clp) {
         // Cluster record: W = C - O and rp_k = R (1 + 2^-20) + (2^-9 + 2^-16) (|W| + R) (C, R: the
-        // cluster's bounding sphere, set_scene; R = -inf: padding, never passes).  A member's rp_i <=
+        // cluster's bounding sphere, cluster_bounds; R = -inf: padding, never passes).  A member's rp_i <=
         // r_i (1 + 2^-21) + (2^-9 + 2^-19) |w_i| (sqrt(64 u) = 2^-9) and |w_i| <= |W| + R, so rp_k >=
         // rp_i + |c_i - C| plus the fp32 evaluation errors of both records (camera_sweep).
         const double R = clus[4 * i + 3];

@@ -20,29 +20,12 @@
 
 #include "../../include/rt_mi355x.h"
 #include "rt_device.hpp"
+#include "rt_formats.hpp"
 #include "rt_experiments.hpp"
 
 namespace rt {
 
-template <typename T> struct MatT {
-    uint32_t kind, hollow;
-    // Lambertian / metal: {albedo r, g, b, fuzz}; dielectric: {ior, 1/ior, r0_front, r0_back} -- the constants
-    // precomputed on the host in T with the reference's operations (IEEE, no contraction, so the bits equal the
-    // per-ray device computation): 1/ior (materials.rs:131) and Schlick's r0 = ((1-ratio)/(1+ratio))^2
-    // (materials.rs:122) for ratio = 1/ior and ior.  Only the fields of the record's kind: fp64 40 bytes, fp32 24.
-    T p[4];
-};
-
-// Device sphere layout (rt_context_set_scene): 64-byte groups, one s_load_dwordx16 each, padded
-// with never-hit dummies (r^2 = -inf makes the discriminant -inf) to whole groups.
-//   fp32: 4 spheres per group as 2 pair-interleaved records {cx0,cx1, cy0,cy1, cz0,cz1, r0,r1}
-//         so each quantity of a sphere pair is an adjacent SGPR pair for packed-FP32 VALU ops;
-//   fp64: 2 spheres per group as {cx, cy, cz, r^2}.
-// A separate AoS table {cx, cy, cz, r^2} per sphere serves the per-lane finalize gather.
-// The filter stream (both precisions) is fp32 in the fp32 layout, with r^2 replaced by the filter's
-// r2f: r^2 rounded up to fp32, +inf for "always exact" spheres, -inf for dummies (see
-// general_sweep).
-template <typename T> constexpr uint32_t kGroup = 64 / (4 * sizeof(T));
+// The scene's group layouts (kGroup, kBoxFloats) and MatT: rt_formats.hpp.
 template <typename T> struct alignas(64) SphGroup { T v[64 / sizeof(T)]; };
 
 // One 64-byte scalar load worth of spheres (s_load_dwordx16 into SGPRs).
@@ -58,9 +41,7 @@ __device__ __forceinline__ SphGroup<T> load_group(const __attribute__((address_s
 typedef float f2 __attribute__((ext_vector_type(2)));
 struct Q4 { uint32_t x, y, z, w; };
 
-// One top group of the general sweep: 4 cluster boxes {centre, half-extent} (pack_sweep), 96 bytes,
-// pair-interleaved like SphGroup: pair q at 12 q, {cx0,cx1, cy0,cy1, cz0,cz1, hx0,hx1, hy0,hy1, hz0,hz1}.
-constexpr uint32_t kBoxFloats = 24;
+// One top group of the general sweep (kBoxFloats floats; layout at rt_formats.hpp).
 struct alignas(32) BoxGroup { float v[kBoxFloats]; };
 __device__ __forceinline__ BoxGroup load_box(const __attribute__((address_space(4))) float* f, uint32_t g) {
     BoxGroup r;
@@ -86,7 +67,7 @@ template <typename T> struct KParams {
     unsigned long long* segs;  // kSegShards shards of kSegStride counters (256 B per shard; direct_sky_samples at slot 16)
     uint32_t* err;
     uint32_t* counter;         // next block of work items (guided_block)
-    uint32_t blk_g;            // largest block (a power of two <= kMaxBlock; launch_t)
+    uint32_t blk_g;            // largest block (a power of two <= kMaxBlock; claim_block)
     uint32_t n_items;
     char* scratch;             // per-wave scratch regions
     size_t scratch_stride;
@@ -98,7 +79,7 @@ template <typename T> struct KParams {
     uint32_t n_fgroups;
     float f_cmax, f_r2max;     // filter margin bounds: max |c|_1 and max r2f over non-exact spheres
     float f_r2min;             // min r2f over non-exact spheres (after the host's floor)
-    float f_ir2, f_hir2, f_isr; // 1/r2min, 0.5/r2min and 8 u/sqrt(r2min), rounded up (launch_t)
+    float f_ir2, f_hir2, f_isr; // 1/r2min, 0.5/r2min and 8 u/sqrt(r2min), rounded up (build_scene_image)
     const float* cull;         // camera cone-cull records {wx, wy, wz, rp} per slot of the sweep layout
     const float* cullc;        // ... and per cluster, then per super (build_cam_table)
     uint32_t n_clp, n_supc;    // cluster records (x64), super records after them (x64; 0: none)
@@ -114,7 +95,7 @@ template <typename T> struct KParams {
     const float* fmeg;         // mega boxes (4 supers each), 4 per group; n_mg groups, 0: no mega level
     uint32_t n_mg;
     // MEGA kernels: the sphere filter in cluster-local frames (pack_local): filter groups with centres
-    // relative to their cluster's centre, inline with each cluster's records (set_scene's inline_stream: the
+    // relative to their cluster's centre, inline with each cluster's records (rt_layout.hpp's inline_stream: the
     // scene indices, and the frame {Cx, Cy, Cz, Rc} / {r2max, 1/r2min} in the r^2 words of records 0 / 1)
     const float* lfsph;
     const float* lclb;         // ... the box levels in group-local frames (pack_local_boxes): per super its
@@ -172,8 +153,6 @@ constexpr uint64_t kW6PixelsPerWave = 24;
 // (4 MB per XCD) push HBM writes from 23 to 41 B/sample, so the default stays at 6
 template <typename T> constexpr int kWavesModes = sizeof(T) == 4 ? 6 : 4;   // ROOT2 and semantics modes
 constexpr int kSegStride = 32;  // u64 per shard (256 B)
-constexpr float kFilterMargin = 48.0f * 0x1.0p-24f;   // general-sweep filter margin factor (nearest_hit)
-constexpr double kExactRatio = 8.0;  // spheres with |c|_1 + r > kExactRatio x the median are "always exact"
 
 // Executed-work counters (product build): per wave, the wave-level tests the culls and
 // exact tests actually run, one LDS add per sweep or camera batch, flushed to shard slots

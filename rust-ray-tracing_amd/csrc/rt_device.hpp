@@ -157,7 +157,7 @@ __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
 // scatter at bounce k.  fp64 takes two 53-bit uniforms from Philox4x32-10, counter (sample, pixel, k,
 // stream), key (k0, k1) = (seed lo, seed hi).  fp32 needs only two 24-bit uniforms, so it draws
 // Philox2x32-10 with counter (pixel, sample | code << 20), code = 0 / 1 + k / 257 + k, and the 32-bit key
-// k0 = seed lo ^ fmix32(seed hi), folded by the host (launch_t; k1 = 0 unused): half the multiplies (round 5,
+// k0 = seed lo ^ fmix32(seed hi), folded by the host (frame_params; k1 = 0 unused): half the multiplies (round 5,
 // same-box C fp32 +1.9 %).  The host keeps the counter injective: spp <= 2^20 and, in fp32,
 // max_bounces <= RT_MAX_BOUNCES_F32 (257 + k < 2^12).
 template <typename T>

@@ -27,12 +27,14 @@
 //     applies quirk Q3's buffer read ("retire rule") and sums in the reference's order, so fp64
 //     and fp32 results are bit-identical to the CPU restatement in oracle/.
 //
-// Source layout (one translation unit): rt_experiments.hpp (build kinds), rt_common.hpp (layouts,
-// kernel arguments, scalar-load pipelines), rt_sweep.hpp (general sweep), rt_camera.hpp (primary
-// rays, scatter), rt_finish.hpp (replay + reduction), rt_trace.hpp + rt_trace_body.hpp (the persistent kernel),
-// rt_layout.hpp (host-side scene layout), rt_split_plan.hpp (the sample-parallel plan, host only),
-// rt_progressive_plan.hpp (a progressive session's record buffer and sample windows, host only); this
-// file holds the C ABI.
+// Source layout (one translation unit): rt_experiments.hpp (build kinds), rt_formats.hpp (the formats host
+// layout and device code share; no HIP), rt_common.hpp (kernel arguments, scalar-load pipelines),
+// rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (replay + reduction),
+// rt_trace.hpp + rt_trace_body.hpp (the persistent kernel); and, host only, without HIP: rt_layout.hpp (the
+// scene image: every device table of a scene, build_scene_image), rt_split_plan.hpp (the sample-parallel
+// plan), rt_progressive_plan.hpp (a progressive session's record buffer and sample windows).  This file holds
+// the C ABI: the context and its device tables, the launch steps (scene_params, frame_params,
+// ensure_cam_tables, plan_grid) and the three launchers (launch_plain, launch_split, launch_window).
 #include "rt_trace.hpp"
 #include "rt_layout.hpp"
 #include "rt_split_plan.hpp"
@@ -56,60 +58,103 @@ static int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(RT_ERR_HIP, std::string(#x ": ") + hipGetErrorString(e_)); \
     } while (0)
 
+// One hipMalloc and its size; move-only, freed with its owner.
+struct DeviceBuffer {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+        if (this != &o) { reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DeviceBuffer() { reset(); }
+    hipError_t release() {
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        p = nullptr;
+        bytes = 0;
+        return e;
+    }
+    void reset() { (void)release(); }
+    hipError_t alloc(size_t n) {   // n == 0: hipMalloc gives no memory (p stays NULL)
+        reset();
+        const hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n; else p = nullptr;
+        return e;
+    }
+};
+static int upload(DeviceBuffer& d, const void* src, size_t bytes) {
+    HIPCHK(d.alloc(bytes));
+    HIPCHK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+    return RT_OK;
+}
+static int reserve(DeviceBuffer& d, size_t bytes) {
+    HIPCHK(d.alloc(bytes));
+    return RT_OK;
+}
+// A table the scene does not have (empty: the mega levels of a small scene) stays NULL.
+template <typename V> static int upload(DeviceBuffer& d, const std::vector<V>& v) {
+    return v.empty() ? RT_OK : upload(d, v.data(), v.size() * sizeof(V));
+}
+// Grow a buffer the launches of a context share (scratch, records): nothing may still be using the old one.
+static int ensure_bytes(DeviceBuffer& b, size_t bytes, hipStream_t st) {
+    if (bytes <= b.bytes) return RT_OK;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(b.release());
+    HIPCHK(b.alloc(bytes));
+    return RT_OK;
+}
+
+// The device side of SceneTables<T> (rt_layout.hpp), one allocation per table, its constants, and the
+// tables build_cam_table fills at a launch.  The camera tables depend only on the scene, the camera
+// centre, the scalar mode and RT_FILTER_OFF: a launch with the same key reuses them (bench frames, shards).
+template <typename T> struct DeviceScene {
+    DeviceBuffer sph, cen, fsph, rsph, rfsph, top, sup, meg, lfs, lbx[4], clus, mats;
+    DeviceBuffer cam, camf, camx, cull, cullc;   // camera-origin, camera filter, per-sphere, cone-cull, per-cluster
+    TableConsts k;
+    struct CamKey { bool valid = false; double center[3] = {0, 0, 0}; uint32_t scalar = 0, off = 0; } camkey;
+    void reset() { *this = DeviceScene(); }
+};
+template <typename T> static int upload_scene(DeviceScene<T>& d, const SceneTables<T>& t) {
+    int rc = RT_OK;
+    auto up = [&](DeviceBuffer& dst, const auto& v) { if (rc == RT_OK) rc = upload(dst, v); };
+    auto room = [&](DeviceBuffer& dst, size_t bytes) { if (rc == RT_OK) rc = reserve(dst, bytes); };
+    up(d.sph, t.sph); up(d.cen, t.cen); up(d.fsph, t.fsph);
+    up(d.rsph, t.rsph); up(d.rfsph, t.rfsph);
+    up(d.top, t.top); up(d.sup, t.sup); up(d.meg, t.meg);
+    up(d.lfs, t.lfs);
+    for (int lv = 0; lv < 4; ++lv) up(d.lbx[lv], t.lbx[lv]);
+    up(d.clus, t.clus); up(d.mats, t.mats);
+    room(d.cam, t.cam_bytes.cam); room(d.camf, t.cam_bytes.camf); room(d.camx, t.cam_bytes.camx);
+    room(d.cull, t.cam_bytes.cull); room(d.cullc, t.cam_bytes.cullc);
+    d.k = t.k;
+    return rc;
+}
+
 struct rt_context {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev_first = nullptr, ev_last = nullptr;
     bool have_first = false;
-    // scene, fp64 and fp32 images
-    void* sph64 = nullptr; void* sph32 = nullptr;   // grouped sphere records
-    void* fsph64 = nullptr; void* fsph32 = nullptr; // fp32 filter streams (for fp64 / fp32 rays)
-    uint32_t n_fgroups = 0;
-    float f_cmax64 = 0, f_r2max64 = 0, f_cmax32 = 0, f_r2max32 = 0, f_r2min64 = 0, f_r2min32 = 0;
-    void* cam64 = nullptr; void* cam32 = nullptr;   // camera-origin tables (same size; rebuilt per launch)
-    void* camf64 = nullptr; void* camf32 = nullptr; // camera filter tables (fp32 layout; rebuilt per launch)
-    void* cen64 = nullptr; void* cen32 = nullptr;   // AoS centre tables
-    void* camx64 = nullptr; void* camx32 = nullptr; // per-sphere camera-origin records (rebuilt per launch)
-    void* cull64 = nullptr; void* cull32 = nullptr; // camera cone-cull records (fp32; rebuilt per launch)
-    uint32_t n_cull = 0;                            // records: n_spheres rounded up to 64, + 64 padding
-    void* rsph64 = nullptr; void* rsph32 = nullptr; // general sweep: slot-order exact groups
-    void* rfsph64 = nullptr; void* rfsph32 = nullptr; // slot-order fp32 filter groups
-    void* top64 = nullptr; void* top32 = nullptr;   // cluster bounds (fp32 top groups)
-    void* sup64 = nullptr; void* sup32 = nullptr;   // super boxes (4 clusters each)
-    void* meg64 = nullptr; void* meg32 = nullptr;   // mega boxes (4 supers each; big scenes only)
-    void* lfs64 = nullptr; void* lfs32 = nullptr;   // cluster-local filter groups (big scenes only)
-    void* lbx64[4] = {}; void* lbx32[4] = {};       // local box levels: cluster boxes, supers, megas, gigas
-    uint32_t n_gg = 0;
-    float l_r2max64 = 0, l_r2min64 = 0, l_r2max32 = 0, l_r2min32 = 0;
-    uint32_t n_mg = 0;
-    void* mtiers = nullptr;                         // the mega walk's order table (pack_mega_tiers)
-    float mt_lo[3] = {0, 0, 0}, mt_inv = 0;
-    uint32_t mt_n[3] = {1, 1, 1};
-    uint32_t* ridx = nullptr;
-    void* clus64 = nullptr; void* clus32 = nullptr;   // cluster bounding spheres {C, R} (double)
-    void* cullc64 = nullptr; void* cullc32 = nullptr; // per-cluster camera cull records (rebuilt per launch)
-    uint32_t n_cslots = 0, n_clp = 0;                 // slot-order cull records; cluster records (x64)
-    uint32_t n_supc = 0;                              // super records after them (x64; 0: none)
-    uint32_t n_top = 0, n_xg = 0, n_xs = 0;
-    uint32_t n_groups64 = 0, n_groups32 = 0;
-    void* mat64 = nullptr; void* mat32 = nullptr;     // per-sphere material records
-    uint32_t n_spheres = 0, n_materials = 0;
-    unsigned long long* segs = nullptr;
-    uint32_t* err = nullptr;
-    uint32_t* counter = nullptr;   // persistent-kernel claim-stream counters (zeroed before each launch)
-    void* scratch = nullptr;       // per-wave ray state (grown on demand)
-    size_t scratch_bytes = 0;
-    void* records = nullptr;       // the sample-parallel path's record buffer (grown on demand)
-    size_t records_bytes = 0;
+    // the scene: the tables of each precision, what both share, and the image's counts
+    DeviceScene<float> d32;
+    DeviceScene<double> d64;
+    DeviceBuffer ridx, mtiers;   // slot -> scene index; the mega walk's order table (pack_mega_tiers)
+    SceneCounts n;
+    template <typename T> DeviceScene<T>& scene() {
+        if constexpr (sizeof(T) == 8) return d64; else return d32;
+    }
+    DeviceBuffer segs, err;
+    DeviceBuffer counter;   // persistent-kernel claim-stream counters (zeroed before each launch)
+    DeviceBuffer scratch;   // per-wave ray state (grown on demand)
+    DeviceBuffer records;   // the sample-parallel path's record buffer (grown on demand)
     int n_cu = 0;
     uint64_t samples = 0, pixels = 0;
     hipStream_t last_stream = nullptr;   // stream of the previous render (they share scratch and tables)
     bool have_last = false;
-    // The camera tables of each precision (build_cam_table) depend only on the scene, the camera centre,
-    // the scalar mode and RT_FILTER_OFF: a launch with the same key reuses them (bench frames, shards).
-    uint64_t scene_gen = 0;
-    struct CamKey { bool valid = false; uint64_t gen = 0; double center[3] = {0, 0, 0}; uint32_t scalar = 0, off = 0; };
-    CamKey camkey[2];   // [0] fp32 tables, [1] fp64
     uint32_t last_kernel_id = 0, last_wg_per_cu = 0;   // rt_stats.kernel_id / kernel_wg_per_cu of the last launch
     // The progressive session (rt_progressive_*): what rt_progressive_begin fixed, the samples every pixel's
     // region holds so far, and the record buffer, which only the session's launches touch.
@@ -175,51 +220,23 @@ extern "C" int rt_context_create(int device, rt_context** out) {
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreate(&c->ev_first));
     HIPCHK(hipEventCreate(&c->ev_last));
-    HIPCHK(hipMalloc((void**)&c->segs, sizeof(unsigned long long) * kSegShards * kSegStride));
-    HIPCHK(hipMalloc((void**)&c->err, 16));
-    HIPCHK(hipMalloc((void**)&c->counter, kStreams * kCtrStride * sizeof(uint32_t)));   // claim streams (rt_trace.hpp)
+    HIPCHK(c->segs.alloc(sizeof(unsigned long long) * kSegShards * kSegStride));
+    HIPCHK(c->err.alloc(16));
+    HIPCHK(c->counter.alloc(kStreams * kCtrStride * sizeof(uint32_t)));   // claim streams (rt_trace.hpp)
     HIPCHK(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device));
-    HIPCHK(hipMemset(c->segs, 0, sizeof(unsigned long long) * kSegShards * kSegStride));
-    HIPCHK(hipMemset(c->err, 0, 16));
+    HIPCHK(hipMemset(c->segs.p, 0, c->segs.bytes));
+    HIPCHK(hipMemset(c->err.p, 0, 16));
     *out = c;
     return RT_OK;
 }
 
+// A context without a scene: no table, every count zero.
 static void free_scene(rt_context* c) {
-    (void)hipFree(c->sph64); (void)hipFree(c->sph32); (void)hipFree(c->mat64); (void)hipFree(c->mat32);
-    (void)hipFree(c->cam64); (void)hipFree(c->cam32);
-    c->cam64 = c->cam32 = nullptr;
-    (void)hipFree(c->camf64); (void)hipFree(c->camf32);
-    c->camf64 = c->camf32 = nullptr;
-    (void)hipFree(c->fsph64); (void)hipFree(c->fsph32);
-    c->fsph64 = c->fsph32 = nullptr;
-    (void)hipFree(c->cen64); (void)hipFree(c->cen32);
-    (void)hipFree(c->camx64); (void)hipFree(c->camx32); (void)hipFree(c->cull64); (void)hipFree(c->cull32);
-    c->camx64 = c->camx32 = c->cull64 = c->cull32 = nullptr;
-    (void)hipFree(c->rsph64); (void)hipFree(c->rsph32); (void)hipFree(c->rfsph64); (void)hipFree(c->rfsph32);
-    (void)hipFree(c->top64); (void)hipFree(c->top32); (void)hipFree(c->ridx);
-    (void)hipFree(c->sup64); (void)hipFree(c->sup32);
-    c->sup64 = c->sup32 = nullptr;
-    (void)hipFree(c->meg64); (void)hipFree(c->meg32);
-    (void)hipFree(c->lfs64); (void)hipFree(c->lfs32);
-    c->lfs64 = c->lfs32 = nullptr;
-    for (int lv = 0; lv < 4; ++lv) {
-        (void)hipFree(c->lbx64[lv]); (void)hipFree(c->lbx32[lv]);
-        c->lbx64[lv] = c->lbx32[lv] = nullptr;
-    }
-    c->meg64 = c->meg32 = nullptr;
-    c->n_mg = 0;
-    c->n_gg = 0;
-    (void)hipFree(c->mtiers);
-    c->mtiers = nullptr;
-    (void)hipFree(c->clus64); (void)hipFree(c->clus32); (void)hipFree(c->cullc64); (void)hipFree(c->cullc32);
-    c->clus64 = c->clus32 = c->cullc64 = c->cullc32 = nullptr;
-    c->n_cslots = c->n_clp = c->n_supc = 0;
-    c->rsph64 = c->rsph32 = c->rfsph64 = c->rfsph32 = c->top64 = c->top32 = nullptr;
-    c->ridx = nullptr;
-    c->n_top = c->n_xg = c->n_xs = 0;
-    c->sph64 = c->sph32 = c->mat64 = c->mat32 = c->cen64 = c->cen32 = nullptr;
-    c->n_spheres = c->n_materials = 0;
+    c->d32.reset();
+    c->d64.reset();
+    c->ridx.reset();
+    c->mtiers.reset();
+    c->n = SceneCounts{};
 }
 
 extern "C" int rt_context_destroy(rt_context* c) {
@@ -228,8 +245,7 @@ extern "C" int rt_context_destroy(rt_context* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->prog.open) (void)rt_progressive_end(c);
     free_scene(c);
-    (void)hipFree(c->segs); (void)hipFree(c->err); (void)hipFree(c->counter); (void)hipFree(c->scratch);
-    (void)hipFree(c->records);
+    c->segs.reset(); c->err.reset(); c->counter.reset(); c->scratch.reset(); c->records.reset();
     (void)hipEventDestroy(c->ev_first); (void)hipEventDestroy(c->ev_last);
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -251,177 +267,17 @@ extern "C" int rt_context_set_scene(rt_context* c, const rt_scene* s) {
             return fail(RT_ERR_INVALID, "rt_context_set_scene: unknown material kind (materials.rs:31 would panic)");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    free_scene(c);
-    ++c->scene_gen;   // camera tables built for the previous scene are stale
-    c->camkey[0].valid = c->camkey[1].valid = false;
-    std::vector<double> g64, c64; std::vector<MatT<double>> m64;
-    std::vector<float> g32, c32; std::vector<MatT<float>> m32;
-    pack_scene(s, g64, c64, m64, c->n_groups64);
-    pack_scene(s, g32, c32, m32, c->n_groups32);
-    std::vector<uint32_t> sm(s->n_spheres ? s->n_spheres : 1, 0);
-    for (uint32_t i = 0; i < s->n_spheres; ++i) sm[i] = s->material[i];
-    auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-        HIPCHK(hipMalloc(dst, bytes));
-        HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return RT_OK;
-    };
-    int rc;
-    if ((rc = up(&c->sph64, g64.data(), g64.size() * sizeof(double))) != RT_OK) return rc;
-    if ((rc = up(&c->sph32, g32.data(), g32.size() * sizeof(float))) != RT_OK) return rc;
-    {
-        std::vector<float> f64g, f32g, fr64, fr32;
-        uint32_t nf = 0;
-        pack_filter(c64, s->n_spheres, f64g, nf, c->f_cmax64, c->f_r2max64, c->f_r2min64, fr64);
-        pack_filter(c32, s->n_spheres, f32g, c->n_fgroups, c->f_cmax32, c->f_r2max32, c->f_r2min32, fr32);
-        if ((rc = up(&c->fsph64, f64g.data(), f64g.size() * sizeof(float))) != RT_OK) return rc;
-        if ((rc = up(&c->fsph32, f32g.data(), f32g.size() * sizeof(float))) != RT_OK) return rc;
-        const SweepLayout L = build_layout(s);
-        std::vector<double> rg64; std::vector<float> rg32, rf64, rf32, t64, t32, s64, s32, m64, m32;
-        std::vector<float> lf64, lf32, lr64, lr32;   // the mega kernels' local streams (uploaded inline below)
-        pack_sweep(c64, fr64, L, rg64, rf64, t64, c->f_cmax64, c->f_r2max64, s64, m64);
-        pack_sweep(c32, fr32, L, rg32, rf32, t32, c->f_cmax32, c->f_r2max32, s32, m32);
-        if ((rc = up(&c->sup64, s64.data(), s64.size() * sizeof(float))) != RT_OK) return rc;
-        if ((rc = up(&c->sup32, s32.data(), s32.size() * sizeof(float))) != RT_OK) return rc;
-        c->n_mg = m32.empty() ? 0u : (uint32_t)(m32.size() / kBoxFloats - 1);   // groups, without the empty one
-        if (c->n_mg) {
-            if ((rc = up(&c->meg64, m64.data(), m64.size() * sizeof(float))) != RT_OK) return rc;
-            if ((rc = up(&c->meg32, m32.data(), m32.size() * sizeof(float))) != RT_OK) return rc;
-            std::vector<float> q64, q32;
-            pack_local(c64, L, t64, lf64, lr64, q64);
-            pack_local(c32, L, t32, lf32, lr32, q32);
-            std::vector<float> b64[4], b32[4];
-            pack_local_boxes(c64, L, q64, b64[0], b64[1], b64[2], b64[3], c->l_r2max64, c->l_r2min64);
-            std::vector<float> wme;
-            pack_local_boxes(c32, L, q32, b32[0], b32[1], b32[2], b32[3], c->l_r2max32, c->l_r2min32, &wme);
-            c->n_gg = L.giga && c->n_mg <= 16u ? (c->n_mg + 3u) / 4u : 0u;
-            {
-                const MegaTiers M = pack_mega_tiers(wme, (L.members.size() / 4 + 3) / 4);
-                if ((rc = up(&c->mtiers, M.t.data(), M.t.size() * sizeof(uint64_t))) != RT_OK) return rc;
-                for (int a = 0; a < 3; ++a) { c->mt_lo[a] = M.lo[a]; c->mt_n[a] = M.n[a]; }
-                c->mt_inv = M.inv;
-            }
-            for (int lv = 0; lv < 4; ++lv) {
-                if ((rc = up(&c->lbx64[lv], b64[lv].data(), b64[lv].size() * sizeof(float))) != RT_OK) return rc;
-                if ((rc = up(&c->lbx32[lv], b32[lv].data(), b32[lv].size() * sizeof(float))) != RT_OK) return rc;
-            }
-        }
-        c->n_top = (uint32_t)(L.members.size() / 4);
-        c->n_xg = L.n_xg;
-        c->n_xs = L.n_xs;
-        // slot -> scene index (0xFFFFFFFF: dummy), padded past the last cluster by one block of 64
-        // (the camera sweep's empty quarters read the slots of cluster index n_clusters)
-        const uint32_t ncl = (uint32_t)L.members.size();
-        c->n_cslots = 4u * L.n_xg + 16u * ncl + 64u;
-        c->n_clp = (ncl + 63u) / 64u * 64u;
-        std::vector<uint32_t> ridx(c->n_cslots, 0xFFFFFFFFu);
-        for (size_t i = 0; i < L.slot.size(); ++i) if (L.slot[i] >= 0) ridx[i] = (uint32_t)L.slot[i];
-        // cluster bounding spheres for the camera cull, per precision: centre = the members' AABB
-        // centre, R >= max |c_i - C| + |r_i| over the members' T-precision centres and radii.  Scenes
-        // with more than 128 clusters (config E) also get super records, the bounding spheres of the
-        // 4 clusters of each super (camera_sweep tests them first), stored after the cluster records.
-        const uint32_t nsup = ncl / 4u;
-        c->n_supc = ncl > 128u ? (nsup + 63u) / 64u * 64u : 0u;
-        auto bounds = [&](auto const& cen, std::vector<double>& out) {
-            out.assign((size_t)4 * ((c->n_clp + c->n_supc) ? c->n_clp + c->n_supc : 1), 0.0);
-            for (size_t k = 0; k < out.size() / 4; ++k) out[4 * k + 3] = -INFINITY;
-            auto sphere = [&](size_t at, uint32_t k0, uint32_t nk) {   // the members of clusters k0 .. k0+nk-1
-                double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-                bool any = false;
-                for (uint32_t k = k0; k < k0 + nk; ++k)
-                    for (uint32_t i : L.members[k]) {
-                        any = true;
-                        for (int a = 0; a < 3; ++a) {
-                            const double r = std::fabs((double)cen[4 * i + 3]);
-                            lo[a] = std::min(lo[a], (double)cen[4 * i + a] - r);
-                            hi[a] = std::max(hi[a], (double)cen[4 * i + a] + r);
-                        }
-                    }
-                if (!any) return;
-                double C[3], R = 0.0;
-                for (int a = 0; a < 3; ++a) C[a] = 0.5 * (lo[a] + hi[a]);
-                for (uint32_t k = k0; k < k0 + nk; ++k)
-                    for (uint32_t i : L.members[k]) {
-                        const double dx = (double)cen[4 * i] - C[0], dy = (double)cen[4 * i + 1] - C[1],
-                                     dz = (double)cen[4 * i + 2] - C[2];
-                        R = std::max(R, std::sqrt(dx * dx + dy * dy + dz * dz) + std::fabs((double)cen[4 * i + 3]));
-                    }
-                out[4 * at] = C[0]; out[4 * at + 1] = C[1]; out[4 * at + 2] = C[2];
-                out[4 * at + 3] = std::isfinite(R) ? R * (1.0 + 0x1.0p-40) : INFINITY;
-            };
-            for (uint32_t k = 0; k < ncl; ++k) sphere(k, k, 1);
-            if (c->n_supc)
-                for (uint32_t k = 0; k < nsup; ++k) sphere(c->n_clp + k, 4 * k, 4);
-        };
-        std::vector<double> cl64, cl32;
-        bounds(c64, cl64);
-        bounds(c32, cl32);
-        if ((rc = up(&c->clus64, cl64.data(), cl64.size() * sizeof(double))) != RT_OK) return rc;
-        if ((rc = up(&c->clus32, cl32.data(), cl32.size() * sizeof(double))) != RT_OK) return rc;
-        HIPCHK(hipMalloc(&c->cullc64, cl64.size() / 4 * 4 * sizeof(float)));
-        HIPCHK(hipMalloc(&c->cullc32, cl32.size() / 4 * 4 * sizeof(float)));
-        if ((rc = up(&c->rsph64, rg64.data(), rg64.size() * sizeof(double))) != RT_OK) return rc;
-        if ((rc = up(&c->rsph32, rg32.data(), rg32.size() * sizeof(float))) != RT_OK) return rc;
-        // General-sweep filter streams, inline layout (nearest_hit): the always-exact groups, then per cluster its 4
-        // filter groups, 4 records of 8 words {r^2 of pair 0 (2), r^2 of pair 1 (2), 4 scene indices} (r^2: the
-        // fp32 scene-frame stream, whose exact test takes the centres from the filter group; in the mega kernels'
-        // local streams the r^2 words of records 0 and 1 hold the cluster's frame record); then a dummy group (the
-        // loop's prefetch).  96 floats per cluster keep every group on its own 64-byte line.  A
-        // taken group's record and a walked cluster's frame are loads from the pointer the walk already holds.
-        auto inline_stream = [&](const std::vector<float>& src, bool r2, const std::vector<float>* frame) {
-            const size_t blk = 96, ngf = src.size() / 16 - 1, nxg = c->n_xg, nk = (ngf - nxg) / 4;
-            std::vector<float> rx((size_t)16 * nxg + blk * nk + 32, 0.0f);
-            for (size_t g = 0; g < 16 * nxg; ++g) rx[g] = src[g];
-            for (size_t k = 0; k < nk; ++k) {
-                float* b = &rx[16 * nxg + blk * k];
-                for (size_t j = 0; j < 64; ++j) b[j] = src[16 * (nxg + 4 * k) + j];
-                for (size_t q = 0; q < 4; ++q) {
-                    const size_t g = nxg + 4 * k + q;
-                    uint32_t rec[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-                    if (r2) for (int h = 0; h < 4; ++h) memcpy(&rec[h], &rg32[16 * g + 8 * (h / 2) + 6 + (h % 2)], 4);
-                    for (int j = 0; j < 4; ++j) rec[4 + j] = 4 * g + j < ridx.size() ? ridx[4 * g + j] : 0xFFFFFFFFu;
-                    memcpy(b + 64 + 8 * q, rec, 32);
-                }
-                if (frame) for (size_t j = 0; j < 4; ++j) { b[64 + j] = (*frame)[8 * k + j]; b[72 + j] = (*frame)[8 * k + 4 + j]; }
-            }
-            for (size_t j = 0; j < 16; ++j) rx[16 * nxg + blk * nk + j] = src[16 * ngf + j];   // the dummy group
-            return rx;
-        };
-        {
-            const std::vector<float> rx32 = inline_stream(rf32, true, nullptr), rx64 = inline_stream(rf64, false, nullptr);
-            if ((rc = up(&c->rfsph32, rx32.data(), rx32.size() * sizeof(float))) != RT_OK) return rc;
-            if ((rc = up(&c->rfsph64, rx64.data(), rx64.size() * sizeof(float))) != RT_OK) return rc;
-        }
-        if (c->n_mg) {
-            const std::vector<float> lx32 = inline_stream(lf32, false, &lr32), lx64 = inline_stream(lf64, false, &lr64);
-            if ((rc = up(&c->lfs32, lx32.data(), lx32.size() * sizeof(float))) != RT_OK) return rc;
-            if ((rc = up(&c->lfs64, lx64.data(), lx64.size() * sizeof(float))) != RT_OK) return rc;
-        }
-        if ((rc = up(&c->top64, t64.data(), t64.size() * sizeof(float))) != RT_OK) return rc;
-        if ((rc = up(&c->top32, t32.data(), t32.size() * sizeof(float))) != RT_OK) return rc;
-        if ((rc = up((void**)&c->ridx, ridx.data(), ridx.size() * sizeof(uint32_t))) != RT_OK) return rc;
-        HIPCHK(hipMalloc(&c->camf64, f64g.size() * sizeof(float)));
-        HIPCHK(hipMalloc(&c->camf32, f32g.size() * sizeof(float)));
+    free_scene(c);   // with it the camera tables built for the previous scene, and their keys
+    const SceneImage im = build_scene_image(s);
+    int rc = upload_scene(c->d64, im.t64);
+    if (rc == RT_OK) rc = upload_scene(c->d32, im.t32);
+    if (rc == RT_OK) rc = upload(c->ridx, im.ridx);
+    if (rc == RT_OK) rc = upload(c->mtiers, im.mtiers);
+    if (rc != RT_OK) {
+        free_scene(c);
+        return rc;
     }
-    HIPCHK(hipMalloc(&c->cam64, g64.size() * sizeof(double)));
-    HIPCHK(hipMalloc(&c->cam32, g32.size() * sizeof(float)));
-    c->n_cull = (s->n_spheres + 63u) / 64u * 64u + 64u;
-    HIPCHK(hipMalloc(&c->camx64, (size_t)4 * c->n_cslots * sizeof(double)));
-    HIPCHK(hipMalloc(&c->camx32, (size_t)4 * c->n_cslots * sizeof(float)));
-    HIPCHK(hipMalloc(&c->cull64, (size_t)4 * c->n_cslots * sizeof(float)));
-    HIPCHK(hipMalloc(&c->cull32, (size_t)4 * c->n_cslots * sizeof(float)));
-    if ((rc = up(&c->cen64, c64.data(), c64.size() * sizeof(double))) != RT_OK) return rc;
-    if ((rc = up(&c->cen32, c32.data(), c32.size() * sizeof(float))) != RT_OK) return rc;
-    {
-        // per-sphere records: next_ray gathers a hit sphere's material in one dependent load
-        std::vector<MatT<double>> s64(sm.size());
-        std::vector<MatT<float>> s32(sm.size());
-        for (size_t i = 0; i < sm.size(); ++i)
-            if (sm[i] < m64.size()) { s64[i] = m64[sm[i]]; s32[i] = m32[sm[i]]; }
-        if ((rc = up(&c->mat64, s64.data(), s64.size() * sizeof(MatT<double>))) != RT_OK) return rc;
-        if ((rc = up(&c->mat32, s32.data(), s32.size() * sizeof(MatT<float>))) != RT_OK) return rc;
-    }
-    c->n_spheres = s->n_spheres;
-    c->n_materials = s->n_materials;
+    c->n = im.n;
     return RT_OK;
 }
 
@@ -431,9 +287,6 @@ static bool check_range(const rt_camera* cam, const rt_tile_range* r) {
     const uint64_t last_row = r->row_begin + (uint64_t)(r->row_count - 1) * r->row_step;
     return last_row < cam->image_height;
 }
-
-static int ensure_scratch(rt_context* c, size_t bytes, hipStream_t st);
-static int ensure_records(rt_context* c, size_t bytes, hipStream_t st);
 
 // The kernel instantiation for (flags, waves-per-SIMD target, camera batches, mega level).  W < 0:
 // the defaults (RT_WAVES unset).  The mega level (scenes with more than 8 super groups) has its own
@@ -502,84 +355,78 @@ static void (*pick_window(bool mega))(WParams<T>) {
     constexpr int W = kWavesSplit<T>;
     return mega ? trace_paths_window<T, W, CAMQ, true> : trace_paths_window<T, W, CAMQ, false>;
 }
-// A render's split: S samples per work item, nsub items per pixel (rt_split_plan.hpp).
-// rec != nullptr: one extend of a progressive session (rt_progressive_plan.hpp).  The launch's spp is the
-// session's new sample count: the trace kernel (trace) covers the window [s_begin, spp) on the item grid
-// s_base + j S, writing regions laid out for cap samples in rec, and finish_window (finish) reduces [0, spp).
-struct SplitShape {
-    uint32_t S, nsub;
-    char* rec = nullptr;
-    uint32_t s_begin = 0, s_base = 0, cap = 0;
-    bool trace = true, finish = true;
-};
 constexpr uint64_t kScratchBudget = 24ull << 30;   // scratch (and record buffer) bytes a launch may ask for
 
-// split: the sample-parallel path (trace_paths_split over (pixel, sample sub-range) items, then
-// finish_records); nullptr: trace_paths.
+// ---- the steps of a launch ----
+// What an entry point asks a launch for.
+struct FrameArgs {
+    const rt_camera* cam;
+    uint32_t depth, spp;
+    uint64_t seed;
+    uint32_t flags;
+    rt_tile_range rg;
+    void* rgb;
+    void* lin;
+};
+// One extend of a progressive session (rt_progressive_plan.hpp).  The launch's spp is the session's new
+// sample count: the trace kernel (trace) covers the window [s_begin, spp) on the item grid s_base + j S,
+// nsub items per pixel, writing regions laid out for cap samples in rec, and finish_window (finish)
+// reduces [0, spp).
+struct SessionWindow {
+    char* rec;
+    uint32_t cap, s_begin, s_base, S, nsub;
+    bool trace, finish;
+};
+
+// The scene's tables, constants and counts, and the context's counters.
 template <typename T>
-static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_t spp, uint64_t seed, uint32_t flags,
-                    const rt_tile_range& rg, void* d_rgb, void* d_lin, hipStream_t st,
-                    const SplitShape* split = nullptr) {
-    KParams<T> p;
-    memset(&p, 0, sizeof(p));
-    const bool f64 = sizeof(T) == 8;
-    p.sph = (const T*)(f64 ? c->sph64 : c->sph32);
-    p.cen = (const T*)(f64 ? c->cen64 : c->cen32);
-    p.n_groups = f64 ? c->n_groups64 : c->n_groups32;
-    p.fsph = (const float*)(f64 ? c->fsph64 : c->fsph32);
-    p.n_fgroups = c->n_fgroups;
-    p.rsph = (const T*)(f64 ? c->rsph64 : c->rsph32);
-    p.rfsph = (const float*)(f64 ? c->rfsph64 : c->rfsph32);
-    p.ftop = (const float*)(f64 ? c->top64 : c->top32);
-    p.fsup = (const float*)(f64 ? c->sup64 : c->sup32);
-    p.fmeg = (const float*)(f64 ? c->meg64 : c->meg32);
-    p.n_mg = c->n_mg;
-    p.lfsph = (const float*)(f64 ? c->lfs64 : c->lfs32);
-    p.lclb = (const float*)(f64 ? c->lbx64[0] : c->lbx32[0]);
-    p.lsup = (const float*)(f64 ? c->lbx64[1] : c->lbx32[1]);
-    p.lmeg = (const float*)(f64 ? c->lbx64[2] : c->lbx32[2]);
-    p.lgig = (const float*)(f64 ? c->lbx64[3] : c->lbx32[3]);
-    p.n_gg = c->n_gg;
-    p.mtiers = (const uint64_t*)c->mtiers;
-    for (int a = 0; a < 3; ++a) { p.mt_lo[a] = c->mt_lo[a]; p.mt_n[a] = c->mt_n[a]; }
-    p.mt_inv = c->mt_inv;
-    {
-        auto up32 = [](double v) -> float {
-            float f = (float)v;
-            if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-            return f;
-        };
-        const double r2m = (double)(f64 ? c->l_r2min64 : c->l_r2min32);
-        p.l_r2max = f64 ? c->l_r2max64 : c->l_r2max32;
-        p.l_hir2 = up32((double)kFilterMargin * 0.5 / r2m);
-        p.l_isr = up32(8.0 * 0x1.0p-24 / std::sqrt(r2m));
-    }
-    p.ridx = c->ridx;
-    p.n_top = c->n_top;
-    p.n_xg = c->n_xg;
-    p.n_xs = c->n_xs;
-    p.f_cmax = f64 ? c->f_cmax64 : c->f_cmax32;
-    p.f_r2max = f64 ? c->f_r2max64 : c->f_r2max32;
-    p.f_r2min = f64 ? c->f_r2min64 : c->f_r2min32;
-    {
-        auto up32 = [](double v) -> float {
-            float f = (float)v;
-            if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-            return f;
-        };
-        const double r2m = (double)p.f_r2min;   // 0 (no filtered sphere) gives +inf: every basis is zero
-        p.f_ir2 = up32(1.0 / r2m);
-        p.f_hir2 = up32(0.5 / r2m);
-        p.f_isr = up32(8.0 * 0x1.0p-24 / std::sqrt(r2m));
-    }
-    bool filter_off = false;
-    {   // diagnostics: every general-sweep and camera-sweep group through the exact test
-        const char* e = getenv("RT_FILTER_OFF");
-        filter_off = e && atoi(e) != 0;
-        if (filter_off) p.f_cmax = std::numeric_limits<float>::infinity();
-    }
-    p.mats = (const MatT<T>*)(f64 ? c->mat64 : c->mat32);
-    p.n_spheres = c->n_spheres;
+static void scene_params(rt_context* c, KParams<T>& p) {
+    const DeviceScene<T>& d = c->scene<T>();
+    const SceneCounts& n = c->n;
+    p.sph = (const T*)d.sph.p;
+    p.cen = (const T*)d.cen.p;
+    p.n_groups = d.k.n_groups;
+    p.fsph = (const float*)d.fsph.p;
+    p.n_fgroups = n.n_fgroups;
+    p.rsph = (const T*)d.rsph.p;
+    p.rfsph = (const float*)d.rfsph.p;
+    p.ftop = (const float*)d.top.p;
+    p.fsup = (const float*)d.sup.p;
+    p.fmeg = (const float*)d.meg.p;
+    p.n_mg = n.n_mg;
+    p.lfsph = (const float*)d.lfs.p;
+    p.lclb = (const float*)d.lbx[0].p;
+    p.lsup = (const float*)d.lbx[1].p;
+    p.lmeg = (const float*)d.lbx[2].p;
+    p.lgig = (const float*)d.lbx[3].p;
+    p.n_gg = n.n_gg;
+    p.mtiers = (const uint64_t*)c->mtiers.p;
+    for (int a = 0; a < 3; ++a) { p.mt_lo[a] = n.mt_lo[a]; p.mt_n[a] = n.mt_n[a]; }
+    p.mt_inv = n.mt_inv;
+    p.l_r2max = d.k.l_r2max;
+    p.l_hir2 = d.k.l_hir2;
+    p.l_isr = d.k.l_isr;
+    p.ridx = (const uint32_t*)c->ridx.p;
+    p.n_top = n.n_top;
+    p.n_xg = n.n_xg;
+    p.n_xs = n.n_xs;
+    p.f_cmax = d.k.f_cmax;
+    p.f_r2max = d.k.f_r2max;
+    p.f_r2min = d.k.f_r2min;
+    p.f_ir2 = d.k.f_ir2;
+    p.f_hir2 = d.k.f_hir2;
+    p.f_isr = d.k.f_isr;
+    p.mats = (const MatT<T>*)d.mats.p;
+    p.n_spheres = n.n_spheres;
+    p.segs = (unsigned long long*)c->segs.p;
+    p.err = (uint32_t*)c->err.p;
+    p.counter = (uint32_t*)c->counter.p;
+}
+
+// The camera, the sample counts, the RNG key, the tile range and the outputs; n_items: one per pixel.
+template <typename T>
+static void frame_params(const FrameArgs& a, KParams<T>& p) {
+    const rt_camera* cam = a.cam;
     p.W = cam->image_width; p.H = cam->image_height;
     p.rW = p.W < (1u << 20) ? 1.0 / (double)p.W : 0.0;   // div_dim
     p.rH = p.H < (1u << 20) ? 1.0 / (double)p.H : 0.0;
@@ -587,11 +434,11 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
         p.center[i] = (T)cam->center[i]; p.ulc[i] = (T)cam->ulc[i]; p.vu[i] = (T)cam->vu[i];
         p.vv[i] = (T)cam->vv[i]; p.du[i] = (T)cam->du[i]; p.dv[i] = (T)cam->dv[i];
     }
-    p.spp = spp;
-    p.C = (spp + 3) / 4;
+    p.spp = a.spp;
+    p.C = (a.spp + 3) / 4;
     p.P = 4 * p.C;
-    p.depth = depth;
-    p.flags = flags;
+    p.depth = a.depth;
+    p.flags = a.flags;
     {
         bool pinhole = true;
         for (int i = 0; i < 3; ++i) {
@@ -604,65 +451,92 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
     // fp64: Philox4x32-10 keyed by (seed lo, seed hi).  fp32: Philox2x32-10 has a 32-bit key, folded here as
     // seed lo ^ fmix32(seed hi) (rng<float> reads k0 only): fmix32(0) = 0, so a seed below 2^32 keys as itself,
     // and seeds such as (m << 32) | m no longer all key as 0.
-    if (f64) { p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); }
-    else { p.k0 = (uint32_t)seed ^ fmix32((uint32_t)(seed >> 32)); p.k1 = 0u; }
+    if (sizeof(T) == 8) { p.k0 = (uint32_t)a.seed; p.k1 = (uint32_t)(a.seed >> 32); }
+    else { p.k0 = (uint32_t)a.seed ^ fmix32((uint32_t)(a.seed >> 32)); p.k1 = 0u; }
+    const rt_tile_range& rg = a.rg;
     p.row_begin = rg.row_begin; p.row_step = rg.row_step; p.col_begin = rg.col_begin; p.col_count = rg.col_count;
-    p.rgb = (uint8_t*)d_rgb;
-    p.lin = (double*)d_lin;
-    p.segs = c->segs;
-    p.err = c->err;
-    p.counter = c->counter;
+    p.rgb = (uint8_t*)a.rgb;
+    p.lin = (double*)a.lin;
     p.n_items = rg.row_count * rg.col_count;
-    const uint32_t n_pix = p.n_items;
-    if (split) p.n_items = n_pix * split->nsub;   // <= 0x7FFFFFFF (rt_render_split_async)
+    p.swide = paths_wide(p.P, a.depth);
+    p.vbytes = paths_vbytes(p.P, p.swide, (a.flags & RT_FLAG_MODE_VECTORIZED3) != 0u);
+    p.sbytes = paths_sbytes(p.P, sizeof(T), p.swide);
+}
 
-    // Persistent grid: as many 4-wave workgroups as stay resident, never more waves than pixels.
-    // Minimum waves per SIMD the register allocation targets.  RT_WAVES (4..7; read at every
-    // launch, so one process can compare them) overrides it for the live-path kernels (pinhole and
-    // defocus cameras); the ROOT2 and semantics-mode kernels always run at kWavesModes.
-    const char* waves_env = getenv("RT_WAVES");
-    const int W = waves_env && atoi(waves_env) > 0 ? atoi(waves_env) : -1;
-    // Camera batches + camera-origin table when every primary ray starts at the centre.
-    const bool camq = (p.flags & kFlagPinholeInternal) && depth >= 1u;
-    const bool big = (uint64_t)p.n_items >= kW6PixelsPerWave * 24u * (uint64_t)c->n_cu;   // 24 W6 waves per CU
-    const KernelPick<T> pick = camq ? pick_kernel<T, true>(flags, W, p.n_mg > 0, big)
-                                    : pick_kernel<T, false>(flags, W, p.n_mg > 0, big);
-    void (*kern)(KParams<T>) = pick.fn;
-    const SplitPick<T> spick = camq ? pick_split<T, true>(p.n_mg > 0) : pick_split<T, false>(p.n_mg > 0);
-    void (*const wfn)(WParams<T>) = camq ? pick_window<T, true>(p.n_mg > 0) : pick_window<T, false>(p.n_mg > 0);
-    const bool session = split && split->rec != nullptr;
-    const void* const kfn = session ? (const void*)wfn : split ? (const void*)spick.fn : (const void*)kern;
-    const int kW = split ? spick.W : pick.W;
-    if (camq) {
-        p.camsph = (const T*)(f64 ? c->cam64 : c->cam32);
-        p.camf = (const float*)(f64 ? c->camf64 : c->camf32);
-        p.camx = (const T*)(f64 ? c->camx64 : c->camx32);
-        p.cull = (const float*)(f64 ? c->cull64 : c->cull32);
-        const uint32_t n_slots = (p.n_groups + 1) * kGroup<T>, n_fslots = (p.n_fgroups + 1) * 4;
-        p.cullc = (const float*)(f64 ? c->cullc64 : c->cullc32);
-        p.n_clp = c->n_clp;
-        p.n_supc = c->n_supc;
-        const uint32_t n_thr = std::max(std::max(std::max(n_slots, n_fslots), c->n_cull),
-                                        std::max(c->n_cslots, c->n_clp + c->n_supc));
-        rt_context::CamKey& ck = c->camkey[f64 ? 1 : 0];
-        const uint32_t scalar = (flags & RT_FLAG_MODE_SCALAR) ? 1u : 0u;
-        double cen[3] = {(double)p.center[0], (double)p.center[1], (double)p.center[2]};
-        const bool same = ck.valid && ck.gen == c->scene_gen && ck.scalar == scalar && ck.off == (uint32_t)filter_off &&
-                          memcmp(ck.center, cen, sizeof(cen)) == 0;   // bit for bit (-0 is not +0)
-        if (!same) {
-            auto build = scalar ? build_cam_table<T, true> : build_cam_table<T, false>;
-            hipLaunchKernelGGL(build, dim3((n_thr + 255) / 256), dim3(256), 0, st, p.sph, (T*)p.camsph, n_slots,
-                               (float*)p.camf, n_fslots, p.center[0], p.center[1], p.center[2], (uint32_t)filter_off,
-                               (T*)p.camx, (float*)p.cull, c->n_cull, c->n_spheres, c->ridx, c->n_cslots,
-                               (const double*)(f64 ? c->clus64 : c->clus32), (float*)p.cullc, c->n_clp + c->n_supc);
-            HIPCHK(hipGetLastError());
-            ck.valid = true;
-            ck.gen = c->scene_gen;
-            ck.scalar = scalar;
-            ck.off = (uint32_t)filter_off;
-            memcpy(ck.center, cen, sizeof(cen));
-        }
-    }
+// Camera batches + camera-origin tables (every primary ray starts at the centre): point p at the camera
+// tables of this precision and rebuild them unless the last launch left them for the same key.
+template <typename T>
+static int ensure_cam_tables(rt_context* c, KParams<T>& p, uint32_t flags, bool filter_off, hipStream_t st) {
+    DeviceScene<T>& d = c->scene<T>();
+    const SceneCounts& n = c->n;
+    p.camsph = (const T*)d.cam.p;
+    p.camf = (const float*)d.camf.p;
+    p.camx = (const T*)d.camx.p;
+    p.cull = (const float*)d.cull.p;
+    const uint32_t n_slots = (p.n_groups + 1) * kGroup<T>, n_fslots = (p.n_fgroups + 1) * 4;
+    p.cullc = (const float*)d.cullc.p;
+    p.n_clp = n.n_clp;
+    p.n_supc = n.n_supc;
+    const uint32_t n_thr = std::max(std::max(std::max(n_slots, n_fslots), n.n_cull),
+                                    std::max(n.n_cslots, n.n_clp + n.n_supc));
+    auto& ck = d.camkey;
+    const uint32_t scalar = (flags & RT_FLAG_MODE_SCALAR) ? 1u : 0u;
+    double cen[3] = {(double)p.center[0], (double)p.center[1], (double)p.center[2]};
+    const bool same = ck.valid && ck.scalar == scalar && ck.off == (uint32_t)filter_off &&
+                      memcmp(ck.center, cen, sizeof(cen)) == 0;   // bit for bit (-0 is not +0)
+    if (same) return RT_OK;
+    auto build = scalar ? build_cam_table<T, true> : build_cam_table<T, false>;
+    hipLaunchKernelGGL(build, dim3((n_thr + 255) / 256), dim3(256), 0, st, p.sph, (T*)p.camsph, n_slots,
+                       (float*)p.camf, n_fslots, p.center[0], p.center[1], p.center[2], (uint32_t)filter_off,
+                       (T*)p.camx, (float*)p.cull, n.n_cull, n.n_spheres, p.ridx, n.n_cslots,
+                       (const double*)d.clus.p, (float*)p.cullc, n.n_clp + n.n_supc);
+    HIPCHK(hipGetLastError());
+    ck.valid = true;
+    ck.scalar = scalar;
+    ck.off = (uint32_t)filter_off;
+    memcpy(ck.center, cen, sizeof(cen));
+    return RT_OK;
+}
+
+// What every launcher starts with: the kernel arguments of a frame with items_per_pixel work items per
+// pixel (<= 0x7FFFFFFF items in all: the entry points check), and the camera tables where the frame's
+// kernels run camera batches (camq).
+template <typename T>
+static int frame_setup(rt_context* c, const FrameArgs& a, uint32_t items_per_pixel, hipStream_t st, KParams<T>& p,
+                       bool& camq) {
+    memset(&p, 0, sizeof(p));
+    scene_params(c, p);
+    // diagnostics: every general-sweep and camera-sweep group through the exact test
+    const char* e = getenv("RT_FILTER_OFF");
+    const bool filter_off = e && atoi(e) != 0;
+    if (filter_off) p.f_cmax = std::numeric_limits<float>::infinity();
+    frame_params(a, p);
+    p.n_items *= items_per_pixel;
+    camq = (p.flags & kFlagPinholeInternal) && a.depth >= 1u;
+    return camq ? ensure_cam_tables(c, p, a.flags, filter_off, st) : RT_OK;
+}
+
+// G, the largest block of work items a wave claims at once: the largest power of two <= min(kMaxBlock,
+// kBlockSamples / item_spp, items per wave / kBlockShare), raised to kClaimSpp / item_spp (claim rate,
+// rt_trace.hpp) where the share bound would go under it.
+static uint32_t claim_block(uint64_t n_items, uint64_t nblocks, uint32_t item_spp) {
+    const uint64_t per_wave = n_items / (4u * nblocks);
+    const uint64_t g = std::max<uint64_t>({1u, std::min<uint64_t>({(uint64_t)kMaxBlock, kBlockSamples / item_spp,
+                                                                   per_wave / kBlockShare}),
+                                           std::min<uint64_t>((uint64_t)kMaxBlock, (kClaimSpp + item_spp - 1) / item_spp)});
+    uint32_t G = 1;
+    while (2u * G <= g) G *= 2u;
+    // diagnostics (tools/waves_ab.py --block): RT_BLOCK_G overrides the largest block (1..16, a power of two)
+    const char* ge = getenv("RT_BLOCK_G");
+    if (ge && atoi(ge) >= 1 && atoi(ge) <= (int)kMaxBlock && (atoi(ge) & (atoi(ge) - 1)) == 0) G = (uint32_t)atoi(ge);
+    return G;
+}
+
+// Persistent grid of kernel kfn (built for kW waves per SIMD; id: rt_stats.kernel_id): as many 4-wave
+// workgroups as stay resident, never more waves than work items; and the claim block for items of
+// item_spp samples each.
+static int plan_grid(rt_context* c, const void* kfn, int kW, uint32_t id, uint32_t n_items, uint32_t item_spp,
+                     uint64_t& nblocks, uint32_t& blk_g) {
     int per_cu = 0;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, 0));
     if (per_cu < 1) per_cu = 1;
@@ -676,112 +550,173 @@ static int launch_t(rt_context* c, const rt_camera* cam, uint32_t depth, uint32_
         return fail(RT_ERR_UNSUPPORTED, std::string(RT_BUILD_KIND) + " build: " + std::to_string(per_cu) +
                                             " workgroups per CU resident, kernel built for " + std::to_string(kW) +
                                             " (its LDS or registers grew past the occupancy target)");
-    c->last_kernel_id = split ? spick.id : pick.id;   // only a kernel that passed the check is ever reported
+    c->last_kernel_id = id;   // only a kernel that passed the check is ever reported
     c->last_wg_per_cu = (uint32_t)per_cu;
-    uint64_t nblocks = (uint64_t)c->n_cu * (uint64_t)per_cu;
-    const uint64_t need = ((uint64_t)p.n_items + 3) / 4;
+    nblocks = (uint64_t)c->n_cu * (uint64_t)per_cu;
+    const uint64_t need = ((uint64_t)n_items + 3) / 4;
     if (nblocks > need) nblocks = need;
-    {   // G: the largest power of two <= min(kMaxBlock, kBlockSamples / spp, pixels per wave / kBlockShare),
-        // raised to kClaimSpp / spp (claim rate, below) where the share bound would go under it
-        // (the sample-parallel path: an item's samples for spp, items for pixels)
-        const uint32_t ispp = session ? std::max(1u, std::min(split->S, spp - split->s_begin))
-                                      : split ? std::min(split->S, spp) : spp;
-        const uint64_t per_wave = (uint64_t)p.n_items / (4u * nblocks);
-        const uint64_t g = std::max<uint64_t>({1u, std::min<uint64_t>({(uint64_t)kMaxBlock, kBlockSamples / ispp,
-                                                                       per_wave / kBlockShare}),
-                                               std::min<uint64_t>((uint64_t)kMaxBlock, (kClaimSpp + ispp - 1) / ispp)});
-        uint32_t G = 1;
-        while (2u * G <= g) G *= 2u;
-        // diagnostics (tools/waves_ab.py --block): RT_BLOCK_G overrides the largest block (1..16, a power of two)
-        const char* ge = getenv("RT_BLOCK_G");
-        if (ge && atoi(ge) >= 1 && atoi(ge) <= (int)kMaxBlock && (atoi(ge) & (atoi(ge) - 1)) == 0) G = (uint32_t)atoi(ge);
-        p.blk_g = G;
-    }
-    p.swide = paths_wide(p.P, depth);
-    p.vbytes = paths_vbytes(p.P, p.swide, (flags & RT_FLAG_MODE_VECTORIZED3) != 0u);
-    p.sbytes = paths_sbytes(p.P, sizeof(T), p.swide);
-    if (split) {
-        // The trace kernel writes the record buffer (one region per pixel) and needs no scratch; the finish
-        // kernel's waves stride over the pixels, each with a position map of its own in the scratch.
-        p.scratch_stride = (size_t)p.vbytes;
-        uint64_t fblocks = std::min<uint64_t>(((uint64_t)n_pix + 3) / 4, (uint64_t)c->n_cu * 8u);
-        fblocks = std::max<uint64_t>(1u, std::min<uint64_t>(fblocks, kScratchBudget / (4 * p.scratch_stride)));
-        // a session's regions keep the layout of its capacity whatever the count (the width of e, bit 0 of
-        // swide, depends on the depth alone)
-        const uint32_t P_cap = session ? 4u * ((split->cap + 3u) / 4u) : p.P;
-        if (session) p.sbytes = paths_sbytes(P_cap, sizeof(T), p.swide);
-        int rc = session ? RT_OK : ensure_records(c, (size_t)n_pix * p.sbytes, st);
-        if (rc == RT_OK) rc = ensure_scratch(c, p.scratch_stride * fblocks * 4, st);
-        if (rc != RT_OK) return rc;
-        p.scratch = (char*)c->scratch;
-        SParams<T> sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.k = p;
-        sp.rec = session ? split->rec : (char*)c->records;
-        sp.S = split->S;
-        sp.nsub = split->nsub;
-        sp.n_pix = n_pix;
-        if (session) {
-            WParams<T> wp;
-            memset(&wp, 0, sizeof(wp));
-            wp.s = sp;   // the snapshot's counts: finish_window
-            wp.s_begin = split->s_begin;
-            wp.s_base = split->s_base;
-            wp.P_cap = P_cap;
-            if (split->trace) {
-                WParams<T> wt = wp;
-                wt.s.k.P = P_cap;   // the record view's stride (split_records); the trace kernels read no other count
-                HIPCHK(hipMemsetAsync(c->counter, 0, kStreams * kCtrStride * sizeof(uint32_t), st));
-                hipLaunchKernelGGL(wfn, dim3((uint32_t)nblocks), dim3(256), 0, st, wt);
-                HIPCHK(hipGetLastError());
-            }
-            if (split->finish) {
-                hipLaunchKernelGGL(finish_window<T>, dim3((uint32_t)fblocks), dim3(256), 0, st, wp);
-                HIPCHK(hipGetLastError());
-            }
-            return RT_OK;
-        }
-        HIPCHK(hipMemsetAsync(c->counter, 0, kStreams * kCtrStride * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(spick.fn, dim3((uint32_t)nblocks), dim3(256), 0, st, sp);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(finish_records<T>, dim3((uint32_t)fblocks), dim3(256), 0, st, sp);
-        HIPCHK(hipGetLastError());
-        return RT_OK;
-    }
+    blk_g = claim_block(n_items, nblocks, item_spp);
+    return RT_OK;
+}
+
+static int zero_claim_counters(rt_context* c, hipStream_t st) {
+    HIPCHK(hipMemsetAsync(c->counter.p, 0, kStreams * kCtrStride * sizeof(uint32_t), st));
+    return RT_OK;
+}
+
+// trace_paths: one work item per pixel, every sample of it.
+template <typename T>
+static int launch_plain(rt_context* c, const FrameArgs& a, hipStream_t st) {
+    KParams<T> p;
+    bool camq = false;
+    int rc = frame_setup(c, a, 1u, st, p, camq);
+    if (rc != RT_OK) return rc;
+    // Minimum waves per SIMD the register allocation targets.  RT_WAVES (4..7; read at every
+    // launch, so one process can compare them) overrides it for the live-path kernels (pinhole and
+    // defocus cameras); the ROOT2 and semantics-mode kernels always run at kWavesModes.
+    const char* waves_env = getenv("RT_WAVES");
+    const int W = waves_env && atoi(waves_env) > 0 ? atoi(waves_env) : -1;
+    const bool big = (uint64_t)p.n_items >= kW6PixelsPerWave * 24u * (uint64_t)c->n_cu;   // 24 W6 waves per CU
+    const KernelPick<T> pick = camq ? pick_kernel<T, true>(a.flags, W, p.n_mg > 0, big)
+                                    : pick_kernel<T, false>(a.flags, W, p.n_mg > 0, big);
+    uint64_t nblocks = 0;
+    if ((rc = plan_grid(c, (const void*)pick.fn, pick.W, pick.id, p.n_items, a.spp, nblocks, p.blk_g)) != RT_OK) return rc;
     p.scratch_stride = (size_t)p.vbytes + (size_t)kSlots * p.sbytes;
     // Keep the scratch within a fixed budget: fewer resident waves for very large spp.
     const uint64_t max_blocks = kScratchBudget / (4 * p.scratch_stride);
     if (nblocks > max_blocks) nblocks = max_blocks > 0 ? max_blocks : 1;
-    const int rc = ensure_scratch(c, p.scratch_stride * nblocks * 4, st);
-    if (rc != RT_OK) return rc;
-    p.scratch = (char*)c->scratch;
-    HIPCHK(hipMemsetAsync(c->counter, 0, kStreams * kCtrStride * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(kern, dim3((uint32_t)nblocks), dim3(256), 0, st, p);
+    if ((rc = ensure_bytes(c->scratch, p.scratch_stride * nblocks * 4, st)) != RT_OK) return rc;
+    p.scratch = (char*)c->scratch.p;
+    if ((rc = zero_claim_counters(c, st)) != RT_OK) return rc;
+    hipLaunchKernelGGL(pick.fn, dim3((uint32_t)nblocks), dim3(256), 0, st, p);
     HIPCHK(hipGetLastError());
     return RT_OK;
 }
 
-static int ensure_scratch(rt_context* c, size_t bytes, hipStream_t st) {
-    if (bytes <= c->scratch_bytes) return RT_OK;
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipDeviceSynchronize());
-    if (c->scratch) HIPCHK(hipFree(c->scratch));
-    c->scratch = nullptr;
-    c->scratch_bytes = 0;
-    HIPCHK(hipMalloc(&c->scratch, bytes));
-    c->scratch_bytes = bytes;
+// The sample-parallel kernels' arguments over (pixel, sample sub-range) items: the trace kernel writes the record
+// buffer rec (one region per pixel, p.sbytes each) and needs no scratch; the finish kernel's waves stride over
+// the pixels, each with a position map of its own in the scratch (fblocks workgroups of them).
+template <typename T>
+static int split_params(rt_context* c, KParams<T>& p, char* rec, uint32_t S, uint32_t nsub, uint32_t n_pix,
+                        hipStream_t st, SParams<T>& sp, uint64_t& fblocks) {
+    p.scratch_stride = (size_t)p.vbytes;
+    fblocks = std::min<uint64_t>(((uint64_t)n_pix + 3) / 4, (uint64_t)c->n_cu * 8u);
+    fblocks = std::max<uint64_t>(1u, std::min<uint64_t>(fblocks, kScratchBudget / (4 * p.scratch_stride)));
+    const int rc = ensure_bytes(c->scratch, p.scratch_stride * fblocks * 4, st);
+    if (rc != RT_OK) return rc;
+    p.scratch = (char*)c->scratch.p;
+    memset(&sp, 0, sizeof(sp));
+    sp.k = p;
+    sp.rec = rec;
+    sp.S = S;
+    sp.nsub = nsub;
+    sp.n_pix = n_pix;
     return RT_OK;
 }
 
-static int ensure_records(rt_context* c, size_t bytes, hipStream_t st) {
-    if (bytes <= c->records_bytes) return RT_OK;
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipDeviceSynchronize());
-    if (c->records) HIPCHK(hipFree(c->records));
-    c->records = nullptr;
-    c->records_bytes = 0;
-    HIPCHK(hipMalloc(&c->records, bytes));
-    c->records_bytes = bytes;
+// trace_paths_split over nsub items of S samples per pixel (rt_split_plan.hpp), then finish_records.
+template <typename T>
+static int launch_split(rt_context* c, const FrameArgs& a, uint32_t S, uint32_t nsub, hipStream_t st) {
+    KParams<T> p;
+    bool camq = false;
+    int rc = frame_setup(c, a, nsub, st, p, camq);
+    if (rc != RT_OK) return rc;
+    const uint32_t n_pix = p.n_items / nsub;
+    const SplitPick<T> pick = camq ? pick_split<T, true>(p.n_mg > 0) : pick_split<T, false>(p.n_mg > 0);
+    uint64_t nblocks = 0, fblocks = 0;
+    rc = plan_grid(c, (const void*)pick.fn, pick.W, pick.id, p.n_items, std::min(S, a.spp), nblocks, p.blk_g);
+    if (rc != RT_OK) return rc;
+    if ((rc = ensure_bytes(c->records, (size_t)n_pix * p.sbytes, st)) != RT_OK) return rc;
+    SParams<T> sp;
+    if ((rc = split_params(c, p, (char*)c->records.p, S, nsub, n_pix, st, sp, fblocks)) != RT_OK) return rc;
+    if ((rc = zero_claim_counters(c, st)) != RT_OK) return rc;
+    hipLaunchKernelGGL(pick.fn, dim3((uint32_t)nblocks), dim3(256), 0, st, sp);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(finish_records<T>, dim3((uint32_t)fblocks), dim3(256), 0, st, sp);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// One extend of a progressive session: trace_paths_window over the window's items, then finish_window.
+template <typename T>
+static int launch_window(rt_context* c, const FrameArgs& a, const SessionWindow& w, hipStream_t st) {
+    KParams<T> p;
+    bool camq = false;
+    int rc = frame_setup(c, a, w.nsub, st, p, camq);
+    if (rc != RT_OK) return rc;
+    const uint32_t n_pix = p.n_items / w.nsub;
+    const SplitPick<T> pick = camq ? pick_split<T, true>(p.n_mg > 0) : pick_split<T, false>(p.n_mg > 0);
+    void (*const wfn)(WParams<T>) = camq ? pick_window<T, true>(p.n_mg > 0) : pick_window<T, false>(p.n_mg > 0);
+    uint64_t nblocks = 0, fblocks = 0;
+    rc = plan_grid(c, (const void*)wfn, pick.W, pick.id, p.n_items, std::max(1u, std::min(w.S, a.spp - w.s_begin)),
+                   nblocks, p.blk_g);
+    if (rc != RT_OK) return rc;
+    // a session's regions keep the layout of its capacity whatever the count (the width of e, bit 0 of
+    // swide, depends on the depth alone)
+    const uint32_t P_cap = 4u * ((w.cap + 3u) / 4u);
+    p.sbytes = paths_sbytes(P_cap, sizeof(T), p.swide);
+    WParams<T> wp;
+    memset(&wp, 0, sizeof(wp));
+    if ((rc = split_params(c, p, w.rec, w.S, w.nsub, n_pix, st, wp.s, fblocks)) != RT_OK) return rc;   // the snapshot's counts: finish_window
+    wp.s_begin = w.s_begin;
+    wp.s_base = w.s_base;
+    wp.P_cap = P_cap;
+    if (w.trace) {
+        WParams<T> wt = wp;
+        wt.s.k.P = P_cap;   // the record view's stride (split_records); the trace kernels read no other count
+        if ((rc = zero_claim_counters(c, st)) != RT_OK) return rc;
+        hipLaunchKernelGGL(wfn, dim3((uint32_t)nblocks), dim3(256), 0, st, wt);
+        HIPCHK(hipGetLastError());
+    }
+    if (w.finish) {
+        hipLaunchKernelGGL(finish_window<T>, dim3((uint32_t)fblocks), dim3(256), 0, st, wp);
+        HIPCHK(hipGetLastError());
+    }
+    return RT_OK;
+}
+
+// The checks rt_render*_async and rt_progressive_begin share, after their own of the arguments: the flags
+// (live_only: a path that has the live kernels only), the sample and bounce limits, the image and the tile
+// range, which *rg receives (range == NULL: the whole image).  count_name: what the entry point calls spp.
+static int check_frame(const std::string& who, const rt_camera* cam, uint32_t flags, bool live_only,
+                       const char* count_name, uint32_t count, uint32_t max_bounces, const rt_tile_range* range,
+                       rt_tile_range* rg) {
+    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
+    if (live_only) {
+        if (flags & ~RT_FLAG_F32) return fail(RT_ERR_UNSUPPORTED, who + ": the live path only (no RT_FLAG_ROOT2, no RT_FLAG_MODE_*)");
+    } else {
+        const uint32_t modes = flags & (RT_FLAG_MODE_VECTORIZED | RT_FLAG_MODE_SCALAR | RT_FLAG_MODE_VECTORIZED3);
+        if (modes & (modes - 1u))
+            return fail(RT_ERR_INVALID, who + ": the RT_FLAG_MODE_* flags are exclusive");
+    }
+    if (count > (1u << 20)) return fail(RT_ERR_UNSUPPORTED, who + ": " + count_name + " > 2^20");
+    if ((flags & RT_FLAG_F32) && max_bounces > RT_MAX_BOUNCES_F32)   // rng<float>'s counter (rt_device.hpp)
+        return fail(RT_ERR_UNSUPPORTED, who + ": fp32 with max_bounces > RT_MAX_BOUNCES_F32 (3839)");
+    if (cam->image_width == 0 || cam->image_height == 0) return fail(RT_ERR_INVALID, who + ": empty image");
+    if ((uint64_t)cam->image_width * cam->image_height > 0xFFFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": image too large");
+    *rg = range ? *range : rt_tile_range{0, 1, cam->image_height, 0, cam->image_width};
+    if (!check_range(cam, rg)) return fail(RT_ERR_INVALID, who + ": tile range outside the image");
+    return RT_OK;
+}
+
+// Renders on one context share its work counter, scratch and camera tables: a launch on a new
+// stream first waits for the previous stream, so cross-stream use serialises instead of racing.
+// st: NULL = the HIP null stream.
+static int begin_launch(rt_context* c, hipStream_t st) {
+    HIPCHK(hipSetDevice(c->device));
+    if (c->have_last && c->last_stream != st) HIPCHK(hipStreamSynchronize(c->last_stream));
+    c->last_stream = st;
+    c->have_last = true;
+    if (!c->have_first) {
+        HIPCHK(hipEventRecord(c->ev_first, st));
+        c->have_first = true;
+    }
+    return RT_OK;
+}
+static int end_launch(rt_context* c, hipStream_t st, uint64_t pixels, uint64_t samples) {
+    HIPCHK(hipEventRecord(c->ev_last, st));
+    c->pixels += pixels;
+    c->samples += samples;
     return RT_OK;
 }
 
@@ -793,65 +728,42 @@ static int render_async(rt_context* c, const rt_camera* cam, uint32_t max_bounce
     const std::string who = who_;
     if (!c || !cam) return fail(RT_ERR_INVALID, who + ": NULL argument");
     if (spp == 0) return fail(RT_ERR_INVALID, who + ": spp == 0 (the reference panics: 0/0 in to_u8_array)");
-    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
-    {
-        const uint32_t modes = flags & (RT_FLAG_MODE_VECTORIZED | RT_FLAG_MODE_SCALAR | RT_FLAG_MODE_VECTORIZED3);
-        if (modes & (modes - 1u))
-            return fail(RT_ERR_INVALID, who + ": the RT_FLAG_MODE_* flags are exclusive");
-    }
-    if (spp > (1u << 20)) return fail(RT_ERR_UNSUPPORTED, who + ": spp > 2^20");
-    if ((flags & RT_FLAG_F32) && max_bounces > RT_MAX_BOUNCES_F32)   // rng<float>'s counter (rt_device.hpp)
-        return fail(RT_ERR_UNSUPPORTED, who + ": fp32 with max_bounces > RT_MAX_BOUNCES_F32 (3839)");
-    if (cam->image_width == 0 || cam->image_height == 0) return fail(RT_ERR_INVALID, who + ": empty image");
-    if ((uint64_t)cam->image_width * cam->image_height > 0xFFFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "image too large");
-    rt_tile_range rg = range ? *range : rt_tile_range{0, 1, cam->image_height, 0, cam->image_width};
-    if (!check_range(cam, &rg)) return fail(RT_ERR_INVALID, who + ": tile range outside the image");
-    if ((uint64_t)rg.row_count * rg.col_count > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "too many pixels in one call");
+    FrameArgs a{cam, max_bounces, spp, seed, flags, rt_tile_range{}, d_rgb8, d_linear};
+    int rc = check_frame(who, cam, flags, false, "spp", spp, max_bounces, range, &a.rg);
+    if (rc != RT_OK) return rc;
+    const uint64_t n_pix = (uint64_t)a.rg.row_count * a.rg.col_count;
+    if (n_pix > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many pixels in one call");
     const bool f32 = (flags & RT_FLAG_F32) != 0;
-    SplitShape shape{spp, 1u};
+    uint32_t S = spp, nsub = 1u;   // a render's split: S samples per work item, nsub items per pixel
     bool split = false;
     if (split_mode >= 0) {
         if (flags & ~RT_FLAG_F32) return fail(RT_ERR_UNSUPPORTED, who + ": the live path only (no RT_FLAG_ROOT2, no RT_FLAG_MODE_*)");
-        const uint64_t n_pix = (uint64_t)rg.row_count * rg.col_count;
         const uint32_t P = 4u * ((spp + 3u) / 4u);
         const uint64_t rec_bytes = n_pix * paths_sbytes(P, f32 ? 4u : 8u, paths_wide(P, max_bounces));
         if (split_mode == 0) {
             // resident waves of the split kernels: 4-wave workgroups at their occupancy target on every CU
             const uint32_t waves = (uint32_t)c->n_cu * 4u * (uint32_t)(f32 ? kWavesSplit<float> : kWavesSplit<double>);
             uint64_t n_items = 0;
-            const int prc = split_plan(n_pix, spp, waves, &shape.S, &n_items);
+            const int prc = split_plan(n_pix, spp, waves, &S, &n_items);
             if (prc != kPlanOk) return fail(prc, who + ": no plan for this launch shape");
-            shape.nsub = split_nsub(spp, shape.S);
-            split = shape.nsub > 1u && rec_bytes <= kScratchBudget;   // else: this call is rt_render_async
+            nsub = split_nsub(spp, S);
+            split = nsub > 1u && rec_bytes <= kScratchBudget;   // else: this call is rt_render_async
         } else {
             if (samples_per_item == 0 || samples_per_item > (1u << 20))
                 return fail(RT_ERR_INVALID, who + ": samples_per_item outside 1..2^20");
-            shape.S = samples_per_item;
-            shape.nsub = split_nsub(spp, shape.S);
-            if (n_pix * shape.nsub > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many work items in one call");
+            S = samples_per_item;
+            nsub = split_nsub(spp, S);
+            if (n_pix * nsub > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many work items in one call");
             if (rec_bytes > kScratchBudget) return fail(RT_ERR_UNSUPPORTED, who + ": record buffer over the scratch budget");
             split = true;
         }
     }
-    const SplitShape* const sh = split ? &shape : nullptr;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;   // NULL = the HIP null stream
-    // Renders on one context share its work counter, scratch and camera table: a render on a new
-    // stream first waits for the previous stream, so cross-stream use serialises instead of racing.
-    if (c->have_last && c->last_stream != st) HIPCHK(hipStreamSynchronize(c->last_stream));
-    c->last_stream = st;
-    c->have_last = true;
-    if (!c->have_first) {
-        HIPCHK(hipEventRecord(c->ev_first, st));
-        c->have_first = true;
-    }
-    const int rc = f32 ? launch_t<float>(c, cam, max_bounces, spp, seed, flags, rg, d_rgb8, d_linear, st, sh)
-                       : launch_t<double>(c, cam, max_bounces, spp, seed, flags, rg, d_rgb8, d_linear, st, sh);
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = begin_launch(c, st)) != RT_OK) return rc;
+    if (split) rc = f32 ? launch_split<float>(c, a, S, nsub, st) : launch_split<double>(c, a, S, nsub, st);
+    else rc = f32 ? launch_plain<float>(c, a, st) : launch_plain<double>(c, a, st);
     if (rc != RT_OK) return rc;
-    HIPCHK(hipEventRecord(c->ev_last, st));
-    c->pixels += (uint64_t)rg.row_count * rg.col_count;
-    c->samples += (uint64_t)rg.row_count * rg.col_count * spp;
-    return RT_OK;
+    return end_launch(c, st, n_pix, n_pix * spp);
 }
 
 extern "C" int rt_render_async(rt_context* c, const rt_camera* cam, uint32_t max_bounces, uint32_t spp, uint64_t seed,
@@ -889,15 +801,9 @@ extern "C" int rt_progressive_begin(rt_context* c, const rt_camera* cam, uint32_
     if (!c || !cam) return fail(RT_ERR_INVALID, who + ": NULL argument");
     if (c->prog.open) return fail(RT_ERR_INVALID, who + ": a session is already open on this context");
     if (spp_capacity == 0) return fail(RT_ERR_INVALID, who + ": spp_capacity == 0");
-    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
-    if (flags & ~RT_FLAG_F32) return fail(RT_ERR_UNSUPPORTED, who + ": the live path only (no RT_FLAG_ROOT2, no RT_FLAG_MODE_*)");
-    if (spp_capacity > (1u << 20)) return fail(RT_ERR_UNSUPPORTED, who + ": spp_capacity > 2^20");
-    if ((flags & RT_FLAG_F32) && max_bounces > RT_MAX_BOUNCES_F32)
-        return fail(RT_ERR_UNSUPPORTED, who + ": fp32 with max_bounces > RT_MAX_BOUNCES_F32 (3839)");
-    if (cam->image_width == 0 || cam->image_height == 0) return fail(RT_ERR_INVALID, who + ": empty image");
-    if ((uint64_t)cam->image_width * cam->image_height > 0xFFFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": image too large");
-    const rt_tile_range rg = range ? *range : rt_tile_range{0, 1, cam->image_height, 0, cam->image_width};
-    if (!check_range(cam, &rg)) return fail(RT_ERR_INVALID, who + ": tile range outside the image");
+    rt_tile_range rg{};
+    const int frc = check_frame(who, cam, flags, true, "spp_capacity", spp_capacity, max_bounces, range, &rg);
+    if (frc != RT_OK) return frc;
     const uint64_t n_pix = (uint64_t)rg.row_count * rg.col_count;
     // an extend has one work item per pixel at least
     if (n_pix > kSplitMaxItems) return fail(RT_ERR_UNSUPPORTED, who + ": more than 0x7FFFFFFF work items in one extend");
@@ -938,38 +844,24 @@ extern "C" int rt_progressive_extend_async(rt_context* c, uint32_t spp_total, vo
     if (spp_total > s.cap) return fail(RT_ERR_INVALID, who + ": spp_total above the session's spp_capacity");
     const bool f32 = (s.flags & RT_FLAG_F32) != 0;
     const uint64_t n_pix = (uint64_t)s.rg.row_count * s.rg.col_count;
-    SplitShape shape{1u, 1u};
-    shape.rec = (char*)s.rec;
-    shape.cap = s.cap;
-    shape.trace = spp_total > s.done;
-    shape.finish = d_rgb8 != nullptr || d_linear != nullptr;
-    shape.s_begin = shape.s_base = s.done;
-    if (!shape.trace && !shape.finish) return RT_OK;
-    if (shape.trace) {
+    SessionWindow w{(char*)s.rec, s.cap, s.done, s.done, 1u, 1u, spp_total > s.done, d_rgb8 != nullptr || d_linear != nullptr};
+    if (!w.trace && !w.finish) return RT_OK;
+    if (w.trace) {
         const uint32_t waves = (uint32_t)c->n_cu * 4u * (uint32_t)(f32 ? kWavesSplit<float> : kWavesSplit<double>);
-        ProgWindow w;
-        const int prc = progressive_window(n_pix, s.done, spp_total, waves, &w);
+        ProgWindow pw;
+        const int prc = progressive_window(n_pix, s.done, spp_total, waves, &pw);
         if (prc != kPlanOk) return fail(prc, who + ": no plan for this window (more than 0x7FFFFFFF work items)");
-        shape.S = w.S;
-        shape.nsub = w.nsub;
-        shape.s_base = w.base;
+        w.S = pw.S;
+        w.nsub = pw.nsub;
+        w.s_base = pw.base;
     }
-    HIPCHK(hipSetDevice(c->device));
+    const FrameArgs a{&s.cam, s.depth, spp_total, s.seed, s.flags, s.rg, d_rgb8, d_linear};
     hipStream_t st = (hipStream_t)stream;
-    // the serialisation rule of render_async: the session shares the counter, scratch and camera tables
-    if (c->have_last && c->last_stream != st) HIPCHK(hipStreamSynchronize(c->last_stream));
-    c->last_stream = st;
-    c->have_last = true;
-    if (!c->have_first) {
-        HIPCHK(hipEventRecord(c->ev_first, st));
-        c->have_first = true;
-    }
-    const int rc = f32 ? launch_t<float>(c, &s.cam, s.depth, spp_total, s.seed, s.flags, s.rg, d_rgb8, d_linear, st, &shape)
-                       : launch_t<double>(c, &s.cam, s.depth, spp_total, s.seed, s.flags, s.rg, d_rgb8, d_linear, st, &shape);
+    int rc = begin_launch(c, st);   // the session shares the counter, scratch and camera tables
     if (rc != RT_OK) return rc;
-    HIPCHK(hipEventRecord(c->ev_last, st));
-    c->pixels += n_pix;
-    c->samples += n_pix * (uint64_t)(spp_total - s.done);
+    rc = f32 ? launch_window<float>(c, a, w, st) : launch_window<double>(c, a, w, st);
+    if (rc != RT_OK) return rc;
+    if ((rc = end_launch(c, st, n_pix, n_pix * (uint64_t)(spp_total - s.done))) != RT_OK) return rc;
     s.done = spp_total;
     s.stream = st;
     s.have_stream = true;
@@ -994,12 +886,12 @@ extern "C" int rt_context_collect(rt_context* c, void* stream, rt_stats* out) {
     HIPCHK(hipStreamSynchronize(st));
     std::vector<unsigned long long> segs(kSegShards * kSegStride);
     uint32_t err = 0;
-    HIPCHK(hipMemcpy(segs.data(), c->segs, segs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&err, c->err, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(segs.data(), c->segs.p, segs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&err, c->err.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
     float ms = 0.f;
     if (c->have_first) HIPCHK(hipEventElapsedTime(&ms, c->ev_first, c->ev_last));
-    HIPCHK(hipMemset(c->segs, 0, segs.size() * sizeof(unsigned long long)));
-    HIPCHK(hipMemset(c->err, 0, 16));
+    HIPCHK(hipMemset(c->segs.p, 0, segs.size() * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(c->err.p, 0, 16));
     uint64_t total = 0, slots = 0, iters = 0, dsky = 0, kst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, work[kNWork] = {};
     for (int i = 0; i < kSegShards; ++i)
         for (int j = 0; j < 8; ++j) kst[j] += segs[(size_t)i * kSegStride + 3 + j];

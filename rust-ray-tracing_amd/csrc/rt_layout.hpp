@@ -1,10 +1,28 @@
-// rt_layout.hpp — host side of rt_context_set_scene: the device layouts of the scene (grouped
-// sphere records, filter streams, the k-d sweep layout with its box levels, group-local frames and
-// the mega walk's tier table).  Host code only; included by rt_kernel.hip.
+// rt_layout.hpp — the scene image: every device table of a scene, built on the host (grouped sphere
+// records, filter streams, the k-d sweep layout with its box levels, group-local frames, the mega walk's
+// tier table, the camera cull's bounding spheres) and the constants the kernels take with them.
+// build_scene_image() is the entry point; rt_context_set_scene uploads what it returns.  Plain C++, no
+// HIP: it shares rt_formats.hpp with the device code and builds with g++ alone (tests/sanitize/layout_san.cpp).
 #pragma once
-#include "rt_common.hpp"
+#include <stdint.h>
+#include <string.h>
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "../../include/rt_mi355x.h"
+#include "rt_formats.hpp"
 
 using namespace rt;
+
+// The smallest fp32 >= v.
+static inline float round_up_f32(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
+    return f;
+}
 
 // Grouped, padded sphere records (layout at SphGroup) + AoS centre table, in precision T.
 template <typename T>
@@ -64,11 +82,6 @@ static void pack_filter(const std::vector<T>& cen, uint32_t n, std::vector<float
         std::nth_element(k2.begin(), k2.begin() + n / 2, k2.end());
         median = k2[n / 2];
     }
-    auto up32 = [](double v) -> float {   // fp32 >= v
-        float f = (float)v;
-        if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-        return f;
-    };
     // The kernel scales each lane's filter basis by 1/sqrt(1 + m/r2min), which inflates every r2f
     // by the factor (1 + m/r2min) >= 1 + m/r2f.  A floor on r2f (tiny spheres filtered as if of the
     // floor radius, conservative) keeps one tiny sphere from inflating all the others.
@@ -97,7 +110,7 @@ static void pack_filter(const std::vector<T>& cen, uint32_t n, std::vector<float
             if (!finite || key[i] > kExactRatio * median) {
                 f[3] = std::numeric_limits<float>::infinity();
             } else {
-                f[3] = up32(std::max((double)r2, floor2));
+                f[3] = round_up_f32(std::max((double)r2, floor2));
                 cm = std::max(cm, c1);
                 rm = std::max(rm, (double)f[3]);
                 rmin = std::min(rmin, (double)f[3]);
@@ -107,8 +120,8 @@ static void pack_filter(const std::vector<T>& cen, uint32_t n, std::vector<float
         for (int q = 0; q < 4; ++q) grp[(size_t)16 * g + 8 * (j / 2) + 2 * q + (j % 2)] = f[q];   // pair-interleaved
         if (i < n) for (int q = 0; q < 4; ++q) frec[(size_t)4 * i + q] = f[q];
     }
-    cmax = up32(cm);
-    r2max = up32(rm);
+    cmax = round_up_f32(cm);
+    r2max = round_up_f32(rm);
     r2min = std::isfinite(rmin) ? (float)rmin : 0.0f;   // exact: rmin is an fp32 value
 }
 
@@ -251,11 +264,6 @@ template <typename T>
 static void pack_sweep(const std::vector<T>& cen, const std::vector<float>& frec, const SweepLayout& L,
                        std::vector<T>& rgrp, std::vector<float>& rfgrp, std::vector<float>& top, float& cmax,
                        float& r2max, std::vector<float>& sup, std::vector<float>& meg) {
-    auto up32 = [](double v) -> float {
-        float f = (float)v;
-        if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-        return f;
-    };
     const size_t ns = L.slot.size(), nfg = ns / 4;
     constexpr uint32_t G = kGroup<T>, NE = 64 / sizeof(T);
     rgrp.assign((size_t)NE * (ns / G + 1), T(0));
@@ -297,7 +305,7 @@ static void pack_sweep(const std::vector<T>& cen, const std::vector<float>& frec
             for (int a = 0; a < 3; ++a) {
                 b[a] = (float)(0.5 * (lo[a] + hi[a]));
                 const double h = std::max(hi[a] - (double)b[a], (double)b[a] - lo[a]);
-                b[3 + a] = inf ? INFINITY : up32(h * (1.0 + 0x1.0p-20) + 0x1.0p-22 * std::fabs((double)b[a]));
+                b[3 + a] = inf ? INFINITY : round_up_f32(h * (1.0 + 0x1.0p-20) + 0x1.0p-22 * std::fabs((double)b[a]));
                 c1 += std::fabs((double)b[a]) + (double)b[3 + a];
             }
             if (!inf) cm = std::max(cm, c1);
@@ -332,7 +340,7 @@ static void pack_sweep(const std::vector<T>& cen, const std::vector<float>& frec
                     for (int a = 0; a < 3; ++a) {
                         b[a] = inf ? 0.0f : (float)(0.5 * (lo[a] + hi[a]));
                         const double h = std::max(hi[a] - (double)b[a], (double)b[a] - lo[a]);
-                        b[3 + a] = inf ? INFINITY : up32(h * (1.0 + 0x1.0p-20) + 0x1.0p-22 * std::fabs((double)b[a]));
+                        b[3 + a] = inf ? INFINITY : round_up_f32(h * (1.0 + 0x1.0p-20) + 0x1.0p-22 * std::fabs((double)b[a]));
                         c1 += std::fabs((double)b[a]) + (double)b[3 + a];
                     }
                     if (!inf) cm = std::max(cm, c1);
@@ -346,7 +354,7 @@ static void pack_sweep(const std::vector<T>& cen, const std::vector<float>& frec
     unite(top, nsup, sup);
     if (nsg > 8) unite(sup, nsg, meg);
     else meg.clear();
-    cmax = up32(cm);
+    cmax = round_up_f32(cm);
     (void)r2max;
 }
 
@@ -362,11 +370,6 @@ static void pack_sweep(const std::vector<T>& cen, const std::vector<float>& frec
 template <typename T>
 static void pack_local(const std::vector<T>& cen, const SweepLayout& L, const std::vector<float>& top,
                        std::vector<float>& lfgrp, std::vector<float>& lrec, std::vector<float>& r2l) {
-    auto up32 = [](double v) -> float {
-        float f = (float)v;
-        if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-        return f;
-    };
     const size_t ns = L.slot.size(), nc = L.members.size();
     lfgrp.assign((size_t)16 * (ns / 4 + 1), 0.0f);
     for (size_t i = 0; i < ns + 4; ++i) lfgrp[(size_t)16 * (i / 4) + 8 * ((i % 4) / 2) + 6 + (i % 2)] = -INFINITY;
@@ -386,7 +389,7 @@ static void pack_local(const std::vector<T>& cen, const SweepLayout& L, const st
             float f[4];
             for (int a = 0; a < 3; ++a) f[a] = (float)((double)cen[4 * i + a] - (double)Ck[a]);   // RN_f(c - C_k)
             const T r2 = cen[4 * i + 3] * cen[4 * i + 3];
-            f[3] = up32(std::max((double)r2, floor2));
+            f[3] = round_up_f32(std::max((double)r2, floor2));
             if (r2l.size() <= i) r2l.resize((size_t)i + 1, -INFINITY);
             r2l[i] = f[3];
             rc = std::max(rc, std::fabs((double)f[0]) + std::fabs((double)f[1]) + std::fabs((double)f[2]));
@@ -396,9 +399,9 @@ static void pack_local(const std::vector<T>& cen, const SweepLayout& L, const st
         }
         float* r = &lrec[8 * k];
         r[0] = Ck[0]; r[1] = Ck[1]; r[2] = Ck[2];
-        r[3] = up32(rc);
-        r[4] = up32(r2fmax);
-        r[5] = up32(1.0 / r2min);
+        r[3] = round_up_f32(rc);
+        r[4] = round_up_f32(r2fmax);
+        r[5] = round_up_f32(1.0 / r2min);
     }
 }
 
@@ -414,11 +417,6 @@ template <typename T>
 static void pack_local_boxes(const std::vector<T>& cen, const SweepLayout& L, const std::vector<float>& r2l,
                              std::vector<float>& lclb, std::vector<float>& lsup, std::vector<float>& lmeg,
                              std::vector<float>& lgig, float& r2max, float& r2min, std::vector<float>* wmeg = nullptr) {
-    auto up32 = [](double v) -> float {
-        float f = (float)v;
-        if ((double)f < v) f = std::nextafter(f, std::numeric_limits<float>::infinity());
-        return f;
-    };
     const size_t nc = L.members.size();
     // world boxes, BoxGroup layout (4 per 24 floats), like pack_sweep's, around sqrt(local r2f)
     auto put = [](std::vector<float>& v, size_t k, const float b[6]) {
@@ -433,7 +431,7 @@ static void pack_local_boxes(const std::vector<T>& cen, const SweepLayout& L, co
         for (int a = 0; a < 3; ++a) {
             b[a] = inf ? 0.0f : (float)(0.5 * (lo[a] + hi[a]));
             const double h = std::max(hi[a] - (double)b[a], (double)b[a] - lo[a]);
-            b[3 + a] = inf ? INFINITY : up32(h * (1.0 + 0x1.0p-20) + 0x1.0p-22 * std::fabs((double)b[a]));
+            b[3 + a] = inf ? INFINITY : round_up_f32(h * (1.0 + 0x1.0p-20) + 0x1.0p-22 * std::fabs((double)b[a]));
         }
     };
     const float kEmpty[6] = {0.0f, 0.0f, 0.0f, -INFINITY, -INFINITY, -INFINITY};
@@ -458,7 +456,7 @@ static void pack_local_boxes(const std::vector<T>& cen, const SweepLayout& L, co
         box_of(lo, hi, inf, b);
         put(wcl, k, b);
     }
-    r2max = up32(rmax);
+    r2max = round_up_f32(rmax);
     r2min = std::isfinite(rmin) ? (float)rmin : 0.0f;
     auto unite = [&](const std::vector<float>& lower, size_t nup, std::vector<float>& upper) {
         upper.assign((size_t)kBoxFloats * ((nup + 3) / 4 + 1), 0.0f);
@@ -517,7 +515,7 @@ static void pack_local_boxes(const std::vector<T>& cen, const SweepLayout& L, co
                 if (b[3] > -INFINITY) {
                     for (int a = 0; a < 3; ++a) {
                         const float cl = (float)((double)b[a] - (double)Sg[a]);   // RN_f(C - S)
-                        b[3 + a] = b[3 + a] < INFINITY ? up32((double)b[3 + a] + 0x1.0p-22 * std::fabs((double)cl)) : INFINITY;
+                        b[3 + a] = b[3 + a] < INFINITY ? round_up_f32((double)b[3 + a] + 0x1.0p-22 * std::fabs((double)cl)) : INFINITY;
                         b[a] = b[3 + a] < INFINITY ? cl : 0.0f;
                     }
                     rg = std::max(rg, std::fabs((double)b[0]) + std::fabs((double)b[1]) + std::fabs((double)b[2]) +
@@ -526,7 +524,7 @@ static void pack_local_boxes(const std::vector<T>& cen, const SweepLayout& L, co
                 for (int f = 0; f < 6; ++f) o[12 * (j / 2) + 2 * f + (j % 2)] = b[f];
             }
             o[24] = Sg[0]; o[25] = Sg[1]; o[26] = Sg[2];
-            o[27] = std::isfinite(rg) ? up32(rg) : INFINITY;
+            o[27] = std::isfinite(rg) ? round_up_f32(rg) : INFINITY;
         }
     };
     localise(wcl, (nc + 3) / 4, lclb);
@@ -604,4 +602,194 @@ static MegaTiers pack_mega_tiers(const std::vector<float>& wme, size_t nm) {
                 }
             }
     return M;
+}
+
+// Cluster bounding spheres for the camera cull, per precision: centre = the members' AABB
+// centre, R >= max |c_i - C| + |r_i| over the members' T-precision centres and radii.  Scenes
+// with more than 128 clusters (config E) also get super records, the bounding spheres of the
+// 4 clusters of each super (camera_sweep tests them first), stored after the cluster records
+// (n_clp cluster records, then n_supc super records; both multiples of 64).
+template <typename T>
+static void cluster_bounds(const std::vector<T>& cen, const SweepLayout& L, uint32_t n_clp, uint32_t n_supc,
+                           std::vector<double>& out) {
+    const uint32_t ncl = (uint32_t)L.members.size(), nsup = ncl / 4u;
+    out.assign((size_t)4 * ((n_clp + n_supc) ? n_clp + n_supc : 1), 0.0);
+    for (size_t k = 0; k < out.size() / 4; ++k) out[4 * k + 3] = -INFINITY;
+    auto sphere = [&](size_t at, uint32_t k0, uint32_t nk) {   // the members of clusters k0 .. k0+nk-1
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        bool any = false;
+        for (uint32_t k = k0; k < k0 + nk; ++k)
+            for (uint32_t i : L.members[k]) {
+                any = true;
+                for (int a = 0; a < 3; ++a) {
+                    const double r = std::fabs((double)cen[4 * i + 3]);
+                    lo[a] = std::min(lo[a], (double)cen[4 * i + a] - r);
+                    hi[a] = std::max(hi[a], (double)cen[4 * i + a] + r);
+                }
+            }
+        if (!any) return;
+        double C[3], R = 0.0;
+        for (int a = 0; a < 3; ++a) C[a] = 0.5 * (lo[a] + hi[a]);
+        for (uint32_t k = k0; k < k0 + nk; ++k)
+            for (uint32_t i : L.members[k]) {
+                const double dx = (double)cen[4 * i] - C[0], dy = (double)cen[4 * i + 1] - C[1],
+                             dz = (double)cen[4 * i + 2] - C[2];
+                R = std::max(R, std::sqrt(dx * dx + dy * dy + dz * dz) + std::fabs((double)cen[4 * i + 3]));
+            }
+        out[4 * at] = C[0]; out[4 * at + 1] = C[1]; out[4 * at + 2] = C[2];
+        out[4 * at + 3] = std::isfinite(R) ? R * (1.0 + 0x1.0p-40) : INFINITY;
+    };
+    for (uint32_t k = 0; k < ncl; ++k) sphere(k, k, 1);
+    if (n_supc)
+        for (uint32_t k = 0; k < nsup; ++k) sphere(n_clp + k, 4 * k, 4);
+}
+
+// General-sweep filter streams, inline layout (nearest_hit): the always-exact groups, then per cluster its 4
+// filter groups, 4 records of 8 words {r^2 of pair 0 (2), r^2 of pair 1 (2), 4 scene indices} (r^2: the
+// fp32 scene-frame stream, whose exact test takes the centres from the filter group; in the mega kernels'
+// local streams the r^2 words of records 0 and 1 hold the cluster's frame record); then a dummy group (the
+// loop's prefetch).  96 floats per cluster keep every group on its own 64-byte line.  A
+// taken group's record and a walked cluster's frame are loads from the pointer the walk already holds.
+// src: a slot-order filter stream (pack_sweep, pack_local) with n_xg leading always-exact groups; rg32: the
+// fp32 slot-order exact groups the r^2 words come from (nullptr: zero); frame: pack_local's cluster records.
+static std::vector<float> inline_stream(const std::vector<float>& src, size_t n_xg, const std::vector<float>* rg32,
+                                        const std::vector<uint32_t>& ridx, const std::vector<float>* frame) {
+    const size_t blk = 96, ngf = src.size() / 16 - 1, nxg = n_xg, nk = (ngf - nxg) / 4;
+    std::vector<float> rx((size_t)16 * nxg + blk * nk + 32, 0.0f);
+    for (size_t g = 0; g < 16 * nxg; ++g) rx[g] = src[g];
+    for (size_t k = 0; k < nk; ++k) {
+        float* b = &rx[16 * nxg + blk * k];
+        for (size_t j = 0; j < 64; ++j) b[j] = src[16 * (nxg + 4 * k) + j];
+        for (size_t q = 0; q < 4; ++q) {
+            const size_t g = nxg + 4 * k + q;
+            uint32_t rec[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+            if (rg32) for (int h = 0; h < 4; ++h) memcpy(&rec[h], &(*rg32)[16 * g + 8 * (h / 2) + 6 + (h % 2)], 4);
+            for (int j = 0; j < 4; ++j) rec[4 + j] = 4 * g + j < ridx.size() ? ridx[4 * g + j] : 0xFFFFFFFFu;
+            memcpy(b + 64 + 8 * q, rec, 32);
+        }
+        if (frame) for (size_t j = 0; j < 4; ++j) { b[64 + j] = (*frame)[8 * k + j]; b[72 + j] = (*frame)[8 * k + 4 + j]; }
+    }
+    for (size_t j = 0; j < 16; ++j) rx[16 * nxg + blk * nk + j] = src[16 * ngf + j];   // the dummy group
+    return rx;
+}
+
+// ---- the scene image ----
+// The constants the kernels take with one precision's tables.
+struct TableConsts {
+    uint32_t n_groups = 0;                        // groups of sph
+    float f_cmax = 0, f_r2max = 0, f_r2min = 0;   // the filter's margin bounds (pack_filter, pack_sweep)
+    float f_ir2 = 0, f_hir2 = 0, f_isr = 0;       // 1/r2min, 0.5/r2min and 8 u/sqrt(r2min), rounded up
+    float l_r2max = 0, l_r2min = 0;               // the same bounds over the cluster-local r2f (pack_local_boxes)
+    float l_hir2 = 0, l_isr = 0;                  // 48 u 0.5/min and 8 u/sqrt(min), rounded up
+};
+// Bytes of the tables build_cam_table fills at a launch (allocated with the scene, never uploaded).
+struct CamTableBytes { size_t cam = 0, camf = 0, camx = 0, cull = 0, cullc = 0; };
+
+// The tables of one ray precision T, as the device reads them.
+template <typename T> struct SceneTables {
+    std::vector<T> sph, cen;               // grouped sphere records; AoS centre table (pack_scene)
+    std::vector<float> fsph;               // fp32 filter stream (pack_filter)
+    std::vector<T> rsph;                   // general sweep: slot-order exact groups (pack_sweep)
+    std::vector<float> rfsph;              // slot-order filter groups, inline layout (inline_stream)
+    std::vector<float> top, sup, meg;      // cluster boxes, super boxes (4 clusters each), mega boxes (big scenes only)
+    std::vector<float> lfs;                // cluster-local filter groups, inline layout (big scenes only)
+    std::vector<float> lbx[4];             // local box levels: cluster boxes, supers, megas, gigas (big scenes only)
+    std::vector<double> clus;              // cluster (then super) bounding spheres {C, R} (cluster_bounds)
+    std::vector<MatT<T>> mats;             // per-sphere material records (next_ray gathers one in one load)
+    TableConsts k;
+    CamTableBytes cam_bytes;
+};
+// What both precisions share.
+struct SceneCounts {
+    uint32_t n_spheres = 0;
+    uint32_t n_fgroups = 0;                // groups of fsph
+    uint32_t n_top = 0, n_xg = 0, n_xs = 0;
+    uint32_t n_mg = 0, n_gg = 0;           // mega groups (0: no mega level); giga groups (0: no giga pre-test)
+    uint32_t n_cslots = 0, n_clp = 0;      // slot-order cull records; cluster records (x64)
+    uint32_t n_supc = 0;                   // super records after them (x64; 0: none)
+    uint32_t n_cull = 0;                   // n_spheres rounded up to 64, + 64 padding
+    float mt_lo[3] = {0, 0, 0}, mt_inv = 0;   // the grid of mtiers (pack_mega_tiers)
+    uint32_t mt_n[3] = {1, 1, 1};
+};
+struct SceneImage {
+    SceneTables<double> t64;
+    SceneTables<float> t32;
+    std::vector<uint32_t> ridx;            // slot -> scene index (0xFFFFFFFF: dummy)
+    std::vector<uint64_t> mtiers;          // the mega walk's order table (big scenes only)
+    SceneCounts n;
+    template <typename T> const SceneTables<T>& tables() const {
+        if constexpr (sizeof(T) == 8) return t64; else return t32;
+    }
+};
+
+// One precision's tables over the layout L.  wme (fp32 only): the world-frame mega boxes, for pack_mega_tiers.
+template <typename T>
+static void build_tables(const rt_scene* s, const SweepLayout& L, const SceneImage& im, SceneTables<T>& t,
+                         uint32_t& n_fgroups, std::vector<float>* wme) {
+    std::vector<MatT<T>> mats;
+    std::vector<float> frec, rf;
+    pack_scene(s, t.sph, t.cen, mats, t.k.n_groups);
+    pack_filter(t.cen, s->n_spheres, t.fsph, n_fgroups, t.k.f_cmax, t.k.f_r2max, t.k.f_r2min, frec);
+    pack_sweep(t.cen, frec, L, t.rsph, rf, t.top, t.k.f_cmax, t.k.f_r2max, t.sup, t.meg);
+    // the r^2 words of the records: fp32 rays only
+    const std::vector<float>* rg32 = nullptr;
+    if constexpr (sizeof(T) == 4) rg32 = &t.rsph;
+    t.rfsph = inline_stream(rf, L.n_xg, rg32, im.ridx, nullptr);
+    if (!t.meg.empty()) {   // the mega kernels' local streams and box levels
+        std::vector<float> lf, lr, q;
+        pack_local(t.cen, L, t.top, lf, lr, q);
+        pack_local_boxes(t.cen, L, q, t.lbx[0], t.lbx[1], t.lbx[2], t.lbx[3], t.k.l_r2max, t.k.l_r2min, wme);
+        t.lfs = inline_stream(lf, L.n_xg, nullptr, im.ridx, &lr);
+    }
+    cluster_bounds(t.cen, L, im.n.n_clp, im.n.n_supc, t.clus);
+    t.mats.resize(s->n_spheres ? s->n_spheres : 1);   // an empty scene's one slot: material 0
+    for (size_t i = 0; i < t.mats.size(); ++i) {
+        const uint32_t m = i < s->n_spheres ? s->material[i] : 0u;
+        if (m < mats.size()) t.mats[i] = mats[m];
+    }
+    TableConsts& k = t.k;   // the margin constants the kernels take as they are (tests/box_cull_fuzz.c)
+    const double r2m = (double)k.f_r2min;   // 0 (no filtered sphere) gives +inf: every basis is zero
+    k.f_ir2 = round_up_f32(1.0 / r2m);
+    k.f_hir2 = round_up_f32(0.5 / r2m);
+    k.f_isr = round_up_f32(8.0 * 0x1.0p-24 / std::sqrt(r2m));
+    const double l2m = (double)k.l_r2min;
+    k.l_hir2 = round_up_f32((double)kFilterMargin * 0.5 / l2m);
+    k.l_isr = round_up_f32(8.0 * 0x1.0p-24 / std::sqrt(l2m));
+    t.cam_bytes.cam = t.sph.size() * sizeof(T);
+    t.cam_bytes.camf = t.fsph.size() * sizeof(float);
+    t.cam_bytes.camx = (size_t)4 * im.n.n_cslots * sizeof(T);
+    t.cam_bytes.cull = (size_t)4 * im.n.n_cslots * sizeof(float);
+    t.cam_bytes.cullc = t.clus.size() / 4 * 4 * sizeof(float);
+}
+
+// Every table of a valid scene (rt_context_set_scene has checked the arrays and the material indices).
+static SceneImage build_scene_image(const rt_scene* s) {
+    SceneImage im;
+    const SweepLayout L = build_layout(s);
+    const uint32_t ncl = (uint32_t)L.members.size();
+    im.n.n_spheres = s->n_spheres;
+    im.n.n_top = ncl / 4;
+    im.n.n_xg = L.n_xg;
+    im.n.n_xs = L.n_xs;
+    // slot -> scene index, padded past the last cluster by one block of 64
+    // (the camera sweep's empty quarters read the slots of cluster index n_clusters)
+    im.n.n_cslots = 4u * L.n_xg + 16u * ncl + 64u;
+    im.n.n_clp = (ncl + 63u) / 64u * 64u;
+    im.n.n_supc = ncl > 128u ? (ncl / 4u + 63u) / 64u * 64u : 0u;
+    im.n.n_cull = (s->n_spheres + 63u) / 64u * 64u + 64u;
+    im.ridx.assign(im.n.n_cslots, 0xFFFFFFFFu);
+    for (size_t i = 0; i < L.slot.size(); ++i) if (L.slot[i] >= 0) im.ridx[i] = (uint32_t)L.slot[i];
+    uint32_t nf64 = 0;   // n_fgroups is the fp32 call's (the same count)
+    std::vector<float> wme;
+    build_tables(s, L, im, im.t64, nf64, nullptr);
+    build_tables(s, L, im, im.t32, im.n.n_fgroups, &wme);
+    im.n.n_mg = im.t32.meg.empty() ? 0u : (uint32_t)(im.t32.meg.size() / kBoxFloats - 1);   // groups, without the empty one
+    if (im.n.n_mg) {
+        im.n.n_gg = L.giga && im.n.n_mg <= 16u ? (im.n.n_mg + 3u) / 4u : 0u;
+        MegaTiers M = pack_mega_tiers(wme, (L.members.size() / 4 + 3) / 4);
+        for (int a = 0; a < 3; ++a) { im.n.mt_lo[a] = M.lo[a]; im.n.mt_n[a] = M.n[a]; }
+        im.n.mt_inv = M.inv;
+        im.mtiers = std::move(M.t);
+    }
+    return im;
 }

@@ -69,10 +69,10 @@ def test_twins(renderer, prec, path):
     """Every sphere twice, the copies 1 .. 199 indices apart.  hit_update's three tie rules on the device
     (rt_sweep.hpp:173-212): fp64 select, later scene index wins (:208); the fp32 64-bit key
     (bits(t) - bits(0.001f)) << 32 | ~index (:164-166, :191, :204); scalar mode, earlier index wins (:182).  The
-    sweep visits slots, not scene order (rt_layout.hpp:122-123): the two grounds and the 2 x 3 big spheres tie
-    inside the always-exact group (rt_layout.hpp:164, rt_sweep.hpp:562-566), the small ones inside clusters that
+    sweep visits slots, not scene order (rt_layout.hpp, the comment above build_layout): the two grounds and the 2 x 3 big spheres tie
+    inside the always-exact group (build_layout's kBigExact rule, rt_sweep.hpp:562-566), the small ones inside clusters that
     hold both members (their centres are equal, so the k-d splits between them rest on the index tie-break,
-    rt_layout.hpp:202-205), and primary rays tie in camera_exact (rt_camera.hpp:161-162)."""
+    build_layout's nth_element comparator), and primary rays tie in camera_exact (rt_camera.hpp:161-162)."""
     assert_parity(renderer, "twins", es.twins(100, 24, 14), prec | path, spp=12)
 
 
@@ -80,9 +80,9 @@ def test_twins(renderer, prec, path):
 @pytest.mark.parametrize("prec", PRECS)
 def test_twins_mega(renderer, prec, path):
     """2 200 spheres in pairs through the mega kernels: the ties are found in cluster-local frames (the filter
-    sees c' = RN_f(c - C_k), rt_layout.hpp:362-403, rt_sweep.hpp:591-619; the exact test and hit_update see the
+    sees c' = RN_f(c - C_k), pack_local in rt_layout.hpp, rt_sweep.hpp:591-619; the exact test and hit_update see the
     scene-frame values, so equal t stays equal) under group-local boxes (rt_sweep.hpp:438-457).  Scalar mode
-    takes the non-mega kernel over the same layout (pick_kernel, rt_kernel.hip:439)."""
+    takes the non-mega kernel over the same layout (pick_kernel in rt_kernel.hip)."""
     _, st = assert_parity(renderer, "twins_mega", es.twins_mega(), prec | path, spp=16)
     if path == 0:
         assert abi.kernel_info(st.kernel_id)["mega"]
@@ -102,7 +102,7 @@ def test_twins_filter_off_same_image(renderer, prec, monkeypatch):
 @pytest.mark.parametrize("prec", PRECS)
 def test_stack(renderer, prec, path):
     """40 coincident spheres: more than one 16-sphere cluster holds, so one tie spans clusters.  Read from
-    build_layout (rt_layout.hpp:134-242): the ground is always exact (n_xs = 1, n_xg = 1); the 40 are not big
+    build_layout (rt_layout.hpp): the ground is always exact (n_xs = 1, n_xg = 1); the 40 are not big
     (equal radii); the k-d node has zero extent on every axis (:191-198, ax stays 0), nth_element orders by scene
     index alone (:202-205) and splits 40 -> 32 | 8 -> 16 | 16 | 8: clusters {1..16}, {17..32}, {33..40} and one
     empty cluster (n_top = 1).  Their three boxes are the same box (pack_sweep, :283-308: centre (0, 1, 0), h =
@@ -117,8 +117,8 @@ def test_stack(renderer, prec, path):
 @pytest.mark.parametrize("prec", PRECS)
 def test_radii(renderer, prec, path):
     """Radii -1, -0.9 (a bubble), -0.2, 0 and 1e-12, and a -r / +r pair.  pack_scene keeps the signed radius for
-    scalar mode's normal (p - c) / r (rt_layout.hpp:23, objects.rs:242) and squares it for everything else (:27).
-    pack_filter floors r2f at floor2 = max(r2max 2^-10, cmax^2 2^-16) (rt_layout.hpp:85, :100), so the r = 0 and
+    scalar mode's normal (p - c) / r (pack_scene in rt_layout.hpp, objects.rs:242) and squares it for everything else (its field()).
+    pack_filter floors r2f at floor2 = max(r2max 2^-10, cmax^2 2^-16) (rt_layout.hpp), so the r = 0 and
     r = 1e-12 spheres are filtered as spheres of the floor radius and r2min = floor2, which scales every lane's
     basis (rt_sweep.hpp:396) and every box's kappa (rt_sweep.hpp:414).  The camera cull takes |r| (rt_kernel.hip
     :315, :327) and r^2 (rt_camera.hpp:536)."""
@@ -145,7 +145,7 @@ def test_sample_parallel(renderer, name, prec):
 @pytest.mark.parametrize("path", PATHS)
 @pytest.mark.parametrize("prec", PRECS)
 def test_materials(renderer, prec, path):
-    """next_ray's scatter branches (rt_camera.hpp:367-458) on the host's MatT precompute (rt_layout.hpp:38-46):
+    """next_ray's scatter branches (rt_camera.hpp:367-458) on the host's MatT precompute (the end of pack_scene, rt_layout.hpp):
     hollow dielectrics, ior 1.5 and 2.4 (the normal negated before the refraction, rt_camera.hpp:442); fuzz
     exactly 1 and fuzz -0.5 (Metal clamps only above); albedo 1 metal; ior 1 (qf = qb = 0), 0.7, 1e-3 and 1e3
     (inv = 1/ior, qf, qb rounded once on the host in T, :41-45); Lambertian albedo 0 and 1."""
@@ -161,18 +161,18 @@ def test_scaled(renderer, prec, s):
       1e6, 1e12: ordinary lanes, pm = f_cmax + |o|_1 <= 1e15 (rt_sweep.hpp:417), margin ~ 48 u pm^2.
       1e14 and above: f_cmax alone is over 1e15, every lane of the general sweep takes the zero basis and zero
         box times (rt_sweep.hpp:417-421): every box and every sphere passes to the exact test.
-      1e19, fp32 render: the ground's r^2 = 1e44 is +inf in T (always exact, rt_layout.hpp:96-98), the other r2f
+      1e19, fp32 render: the ground's r^2 = 1e44 is +inf in T (always exact: pack_filter's `finite` rule), the other r2f
         are finite (big 1e38, small 4e36 = r2min, f_ir2 = 2.5e-37); |c|^2 overflows in the exact test, every
         discriminant is -inf or NaN; build_cam_table's c = +inf gives sc = +inf (rt_camera.hpp:494-498): sky.
       1e19 and 1e25, fp64 render: the fp32 squares of the cone cull's |w x a| (rt_camera.hpp:69-71) overflow for
         |w| over 1.8e19, f = +inf > rp culled every sphere and the primary rays saw only sky (the first run of
         these cases: 594 of 1008 channels wrong); build_cam_table now gives records with |w| >= 1e18 rp = +inf,
         always tested (kConeWMax, rt_camera.hpp:503-509, :535, :552), next to rup's 1e30 rule (:510-511).
-      1e25, fp32 render: every r^2 is +inf in T, so pack_filter's isfinite rules (rt_layout.hpp:80, :96) make every
+      1e25, fp32 render: every r^2 is +inf in T, so pack_filter's isfinite rules (both of its loops) make every
         r2f +inf and leave cmax = r2max = 0, while build_layout's rule on the fp64 scene (:148) still puts all but
-        the ground into clusters; no sphere is filtered: r2min = 0 (rt_layout.hpp:112), f_ir2 = f_hir2 = f_isr = +inf (rt_kernel.hip:537-540), f_cmax = 0, the cluster
-        boxes have h = +inf and a NaN centre (rt_layout.hpp:298-300), which passes (rt_sweep.hpp:102, NaN: kept).
-      1e25, fp64 render: r2f = up32(4e48) = +inf through the finite branch (rt_layout.hpp:100), so r2max = +inf,
+        the ground into clusters; no sphere is filtered: r2min = 0 (the end of pack_filter), f_ir2 = f_hir2 = f_isr = +inf (build_tables), f_cmax = 0, the cluster
+        boxes have h = +inf and a NaN centre (pack_sweep's cluster boxes), which passes (rt_sweep.hpp:102, NaN: kept).
+      1e25, fp64 render: r2f = round_up_f32(4e48) = +inf through pack_filter's finite branch, so r2max = +inf,
         r2min = 0 as above; the general sweep's lanes are all degenerate, the exact test in double has the range.
     At 1e19 and 1e25 the fp32 oracle renders pure sky with one segment per sample (test_edge_scenes.py); at the
     other scales 59.5 % of the pixels see the scene, in fp64 at every scale."""
@@ -191,7 +191,7 @@ def test_scaled_scalar_f64(renderer, s):
 @pytest.mark.parametrize("prec", PRECS)
 def test_needle(renderer, prec, kind, path):
     """Rays all but parallel to an axis, primary rays included (the -0.0 in the camera centre, or the defocus
-    disk, keeps the launch off the camera batches: rt_kernel.hip:563-568).  down_1e-6: L = fx^2 + fz^2 straddles
+    disk, keeps the launch off the camera batches: frame_params' pinhole test in rt_kernel.hip).  down_1e-6: L = fx^2 + fz^2 straddles
     1e-15 (rt_sweep.hpp:417), 22 % of the primary rays below it, so waves mix lanes with a zero basis and zero
     box times with ordinary lanes whose basis is scaled by rsq(L) up to 3e7 (rt_sweep.hpp:397).  down_1e-30 and
     down_defocus: every primary lane degenerate, the bounced rays ordinary.  along_x: d = (1, 0, 0) exactly or
@@ -213,18 +213,18 @@ def test_needle_filter_off_same_image(renderer, prec, monkeypatch):
 @pytest.mark.parametrize("name", sorted(es.LAYOUT_FAMILIES))
 @pytest.mark.parametrize("prec", PRECS)
 def test_layout_families(renderer, prec, name):
-    """build_layout's untested shapes (rt_layout.hpp:134-242).
+    """build_layout's untested shapes (rt_layout.hpp).
       concentric, collinear, coplanar: k-d nodes with zero extent on 3, 2 and 1 axes (:191-198); the split then
         rests on the comparator's index tie-break (:202-205), in build and in kd_order (:216-235).
       big8: 8 = kBigExact big spheres join the always-exact group and are alone in it (:164-168; n_xs = 8, two
         whole groups, no dummy pair to skip at rt_sweep.hpp:563).  big9: one more and all stay in the clusters.
       uniform, big9, concentric, count1: no always-exact sphere at all: n_xs = n_xg = 0, the exact loop
         (rt_sweep.hpp:562) and cone_walk's first level (rt_camera.hpp:79) run zero times, xw0 is the pad record.
-      count n: 1, 2, 5, 15, 16 (one full cluster), 17 (16 + 1 after the N <= kClusterMax leaf, :186), 33, 64 (one
+      count n: 1, 2, 5, 15, 16 (one full cluster), 17 (16 + 1 after the N <= kClusterMax leaf of its build()), 33, 64 (one
         super), 65 (unit 64: 64 | 1 with the left child's clusters padded to 4, :199-208).
       count1, read: median = the sphere's own key, nothing exact, nothing big (r > 3 r is false), one cluster of
         one member padded to 4 clusters (:212), n_top = 1, slots 0 .. 15 with 15 dummies (r2f = -inf never pass,
-        r^2 = -inf never hit), the super box equals the cluster box, n_mg = 0; launch_t picks the small-launch
+        r^2 = -inf never hit), the super box equals the cluster box, n_mg = 0; launch_plain picks the small-launch
         kernel (fp32 W5, fp64 W4) with camera batches, and the pixel lists hold at most slot 0."""
     flat, cam = es.LAYOUT_FAMILIES[name]()
     assert_parity(renderer, ("layout", name), (flat, cam), prec)

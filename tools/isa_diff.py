@@ -14,6 +14,9 @@ def kernels(path):
     for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
         # (also in the "in Loop: Header=BB12_3" comments: the function's number shifts when kernels are added)
         body = re.sub(r"(?:\.L)?BB\d+_\d+", "L", m.group(2))
+        # a label's trailing comment is padded to a column, so the padding changes with the width of the
+        # function's number (kernels emitted in another order: host code referencing them in another order)
+        body = re.sub(r"^L:[ \t]+;", "L: ;", body, flags=re.M)
         body = re.sub(r"\.Ltmp\d+", "T", body)
         body = re.sub(r"\.Lfunc_end\d+", "E", body)
         out[m.group(1)] = body
