@@ -127,6 +127,9 @@ typedef struct rt_stats {
 /* Set: the sample-parallel kernels ran, trace_paths_split<T, W, CAMQ, MEGA> followed by finish_records<T>
  * (rt_render_split_async); ROOT2 and MODE are 0 there. */
 #define RT_KERNEL_SPLIT(id) (((id) >> 9) & 1u)
+/* Set (with RT_KERNEL_SPLIT): a session's item-table kernel ran, trace_paths_items<T, W, CAMQ, MEGA>
+ * (rt_progressive_extend_map_async with a non-uniform map). */
+#define RT_KERNEL_ITEMS(id) (((id) >> 10) & 1u)
 
 /* ---- flags ---- */
 #define RT_FLAG_F32 0x1u     /* compute in fp32 (default: fp64, the reference's arithmetic) */
@@ -259,6 +262,60 @@ int rt_progressive_begin(rt_context* ctx, const rt_camera* camera, uint32_t max_
  * bounce_iters gets every pixel's K once per reduction, pixels the pixel count once per extend that enqueued
  * work; RT_KERNEL_SPLIT(kernel_id) is set and kernel_ms covers the trace and reduction kernels. */
 int rt_progressive_extend_async(rt_context* ctx, uint32_t spp_total, void* d_rgb8, void* d_linear, void* stream);
+
+/* ---- per-pixel sample counts: stop spending samples on pixels that are converged ----
+ * A session holds done_p samples of pixel p.  "Pixel" is an index in the range's compact order, the order of the
+ * outputs; every array below has one element per pixel of the session's range.  Pixel p's value at n_p samples
+ * is rt_render_async's at spp = n_p for that pixel, bit for bit, whatever the other pixels hold.
+ * A region is still laid out for spp_capacity samples (rt_progressive_bytes): pixels that stop early save
+ * tracing time, not memory. */
+
+/* Trace samples [done_p, spp_target[p]) of every pixel, then, if an output is given, reduce [0, spp_target[p]).
+ * spp_target: HOST array, read before the call returns.  The call may block on copying its own tables (the item
+ * table and the index lists go through a pinned buffer the session owns); the kernels are asynchronous on
+ * `stream`, under the cross-stream rule of rt_render_async.
+ * A map in which every pixel has the same done_p and the same target IS rt_progressive_extend_async (same
+ * kernels, same stats).  Any other map runs one launch of the item-table kernel over the items of
+ * rt_progressive_map_plan, then one reduction launch per distinct target (at most 256 distinct targets when an
+ * output is given: more is RT_ERR_UNSUPPORTED; a trace-only call has no such limit).
+ * RT_ERR_INVALID: no session open, spp_target NULL, a target below done_p or above spp_capacity, a target of 0 with
+ * an output.  With both outputs NULL a target of 0 leaves that pixel untouched.
+ * After a non-uniform map, rt_progressive_extend_async(ctx, n) is RT_ERR_INVALID for n < max done_p and otherwise
+ * traces [done_p, n) of each pixel.
+ * rt_context_collect after it: output pixel p and the return code (RT_ERR_RANGE included) are those of
+ * rt_render_async at spp = spp_target[p].  samples and ray_segments count what was traced since the last collect
+ * (over a session they sum to the unsplit renders' at each pixel's count), bounce_iters gets a pixel's K once per
+ * reduction of that pixel, pixels the pixel count once per call that enqueued work; RT_KERNEL_SPLIT is set, and
+ * RT_KERNEL_ITEMS when the item-table kernel ran. */
+int rt_progressive_extend_map_async(rt_context* ctx, const uint32_t* spp_target, void* d_rgb8, void* d_linear,
+                                    void* stream);
+/* The reduction alone, at any earlier counts: 1 <= spp_count[p] <= done_p (HOST array; NULL = every pixel's
+ * done_p).  Traces nothing: samples and ray_segments are 0 at the collect.
+ * RT_ERR_INVALID: no session open, both outputs NULL, a count of 0 or above done_p; RT_ERR_UNSUPPORTED: more than
+ * 256 distinct counts. */
+int rt_progressive_snapshot_map_async(rt_context* ctx, const uint32_t* spp_count, void* d_rgb8, void* d_linear,
+                                      void* stream);
+/* done_p of every pixel into `out` (host).  Synchronous, no GPU work.  RT_ERR_INVALID: no session, out NULL. */
+int rt_progressive_counts(rt_context* ctx, uint32_t* out);
+/* The half-buffer error estimate, one double per pixel into d_error (device):
+ *   err_p = max over channels of |linear_c at done_p samples - linear_c at done_p / 2 samples| (integer division),
+ * both the session's own linear snapshots, subtracted in double; +inf where done_p < 2.  Runs the two snapshots
+ * into buffers the session owns (48 bytes per pixel), then an element-wise kernel.  Its two reductions count in
+ * bounce_iters like any other (a pixel's K at done_p / 2 and at done_p), and `pixels` gets the pixel count once.
+ * RT_ERR_INVALID: no session open, d_error NULL; RT_ERR_UNSUPPORTED: more than 256 distinct counts. */
+int rt_progressive_error_async(rt_context* ctx, void* d_error, void* stream);
+/* Host only, needs no GPU: the item list rt_progressive_extend_map_async makes for a map.  With A the pixels that
+ * have target > done and mean = ceil(sum (target - done) / A), samples_per_item is rt_split_plan(A, mean,
+ * resident_waves)'s S (0 when A == 0).  Where S is a multiple of 128, pixel p's items are
+ * [max(done_p, base_p + j S), min(target_p, base_p + (j + 1) S)) with base_p = done_p rounded down to 128, so no two
+ * items share a 128-byte line of a pixel's termination-bounce array; any other S makes each active pixel one item
+ * [done_p, target_p).  Items are in pixel order, a pixel's items adjacent.
+ * items: NULL (count only), or room for items_capacity records of 4 words {pixel, first, end, 0}.
+ * RT_ERR_INVALID: a NULL array or output, no pixels, a target below done, items given with items_capacity below
+ * *n_items (which is set); RT_ERR_UNSUPPORTED: a target above 2^20, more than 0x7FFFFFFF pixels or items. */
+int rt_progressive_map_plan(uint64_t n_pixels, const uint32_t* done, const uint32_t* target, uint32_t resident_waves,
+                            uint32_t* samples_per_item, uint64_t* n_items, uint32_t* items, uint64_t items_capacity);
+
 /* Close the session: synchronises the stream of its last extend and frees the record buffer.
  * RT_ERR_INVALID: no session open.  rt_context_destroy ends an open session. */
 int rt_progressive_end(rt_context* ctx);

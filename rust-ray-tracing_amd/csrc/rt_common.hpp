@@ -137,6 +137,23 @@ template <typename T> struct WParams {
     uint32_t P_cap;            // positions a region is laid out for: y[P_cap], c[P_cap], e[P_cap]
 };
 
+// Arguments of a session's per-pixel-count kernels (rt_progressive_extend_map_async): WParams first, at the
+// same kernarg offsets, then one table in device memory.
+//   * trace_paths_items: s.s.k.n_items records {pixel, first, end, 0} of 16 bytes; item i traces the samples
+//     [first, end) of that pixel of the range.  No launch-wide sample count is read (S, nsub, s_begin, s_base and
+//     s.s.k.spp are unused); s.s.k.P and s.s.k.sbytes are the capacity's.
+//   * finish_window_list: s.s.n_pix pixel indices, the pixels that are reduced at the count in s.s.k (one launch
+//     per distinct count).
+struct MapItem { uint32_t pixel, first, end, pad; };
+template <typename T> struct IParams {
+    WParams<T> w;
+    const MapItem* items;
+};
+template <typename T> struct LParams {
+    WParams<T> w;
+    const uint32_t* list;
+};
+
 constexpr int kSegShards = 256;
 constexpr uint32_t kFlagPinholeInternal = 0x80000000u;   // set by the host: defocus vectors are +-0
 constexpr int kWavesF32 = 6;   // default min-waves-per-SIMD targets (measured sweep);
@@ -205,6 +222,17 @@ template <typename T> __device__ __forceinline__ cptr<SParams<T>> cold_split_arg
 // ... and a progressive session's.
 template <typename T> __device__ __forceinline__ cptr<WParams<T>> cold_window_args() {
     cptr<WParams<T>> k = (cptr<WParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+// ... and those of its per-pixel-count kernels.
+template <typename T> __device__ __forceinline__ cptr<IParams<T>> cold_items_args() {
+    cptr<IParams<T>> k = (cptr<IParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+template <typename T> __device__ __forceinline__ cptr<LParams<T>> cold_list_args() {
+    cptr<LParams<T>> k = (cptr<LParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));
     return k;
 }

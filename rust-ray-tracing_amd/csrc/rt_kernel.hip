@@ -34,7 +34,8 @@
 // scene image: every device table of a scene, build_scene_image), rt_split_plan.hpp (the sample-parallel
 // plan), rt_progressive_plan.hpp (a progressive session's record buffer and sample windows).  This file holds
 // the C ABI: the context and its device tables, the launch steps (scene_params, frame_params,
-// ensure_cam_tables, plan_grid) and the three launchers (launch_plain, launch_split, launch_window).
+// ensure_cam_tables, plan_grid) and the launchers (launch_plain, launch_split, launch_window; launch_items and
+// launch_classes for a session's per-pixel counts).
 #include "rt_trace.hpp"
 #include "rt_layout.hpp"
 #include "rt_split_plan.hpp"
@@ -108,6 +109,48 @@ static int ensure_bytes(DeviceBuffer& b, size_t bytes, hipStream_t st) {
     return RT_OK;
 }
 
+// A pinned host buffer that is copied to the device asynchronously, and the event behind its last copy: the
+// host writes it again only after that copy has run.  Move-only, freed with its owner.
+struct PinnedStage {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    PinnedStage() = default;
+    PinnedStage(const PinnedStage&) = delete;
+    PinnedStage& operator=(const PinnedStage&) = delete;
+    PinnedStage& operator=(PinnedStage&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p; bytes = o.bytes; ev = o.ev; pending = o.pending;
+            o.p = nullptr; o.bytes = 0; o.ev = nullptr; o.pending = false;
+        }
+        return *this;
+    }
+    ~PinnedStage() { reset(); }
+    void reset() {
+        if (pending) (void)hipEventSynchronize(ev);
+        if (ev) (void)hipEventDestroy(ev);
+        if (p) (void)hipHostFree(p);
+        p = nullptr; bytes = 0; ev = nullptr; pending = false;
+    }
+};
+// Room for n bytes the host may write now (blocks on the previous copy out of the buffer).
+static int stage_reserve(PinnedStage& g, size_t n) {
+    if (!g.ev) HIPCHK(hipEventCreateWithFlags(&g.ev, hipEventDisableTiming));
+    if (g.pending) {
+        HIPCHK(hipEventSynchronize(g.ev));
+        g.pending = false;
+    }
+    if (n <= g.bytes) return RT_OK;
+    if (g.p) HIPCHK(hipHostFree(g.p));
+    g.p = nullptr;
+    g.bytes = 0;
+    HIPCHK(hipHostMalloc(&g.p, n, hipHostMallocDefault));
+    g.bytes = n;
+    return RT_OK;
+}
+
 // The device side of SceneTables<T> (rt_layout.hpp), one allocation per table, its constants, and the
 // tables build_cam_table fills at a launch.  The camera tables depend only on the scene, the camera
 // centre, the scalar mode and RT_FILTER_OFF: a launch with the same key reuses them (bench frames, shards).
@@ -156,18 +199,25 @@ struct rt_context {
     hipStream_t last_stream = nullptr;   // stream of the previous render (they share scratch and tables)
     bool have_last = false;
     uint32_t last_kernel_id = 0, last_wg_per_cu = 0;   // rt_stats.kernel_id / kernel_wg_per_cu of the last launch
-    // The progressive session (rt_progressive_*): what rt_progressive_begin fixed, the samples every pixel's
-    // region holds so far, and the record buffer, which only the session's launches touch.
+    // The progressive session (rt_progressive_*): what rt_progressive_begin fixed, the samples each pixel's
+    // region holds so far (done, in the range's compact order; done_min == done_max: a uniform session), and the
+    // record buffer, which only the session's launches touch.  The per-pixel-count calls send their tables (the
+    // item table, the classes' index lists, the counts) through stage into tables, and the error estimate keeps
+    // its two linear snapshots in lin_full and lin_half.
     struct Session {
         bool open = false;
         rt_camera cam{};
         rt_tile_range rg{};
-        uint32_t depth = 0, cap = 0, flags = 0, done = 0;
+        uint32_t depth = 0, cap = 0, flags = 0, done_min = 0, done_max = 0;
+        std::vector<uint32_t> done;
         uint64_t seed = 0;
         void* rec = nullptr;
         uint64_t bytes = 0;
-        hipStream_t stream = nullptr;   // of the last extend that enqueued work
+        hipStream_t stream = nullptr;   // of the last call that enqueued work
         bool have_stream = false;
+        PinnedStage stage;
+        DeviceBuffer tables, lin_full, lin_half;
+        void set_done(uint32_t n) { std::fill(done.begin(), done.end(), n); done_min = done_max = n; }
     } prog;
 };
 
@@ -354,6 +404,13 @@ template <typename T, bool CAMQ>
 static void (*pick_window(bool mega))(WParams<T>) {
     constexpr int W = kWavesSplit<T>;
     return mega ? trace_paths_window<T, W, CAMQ, true> : trace_paths_window<T, W, CAMQ, false>;
+}
+// ... and its tracing kernel over an item table (trace_paths_items; RT_KERNEL_ITEMS in the kernel id).
+constexpr uint32_t kKernelItemsBit = 1u << 10;
+template <typename T, bool CAMQ>
+static void (*pick_items(bool mega))(IParams<T>) {
+    constexpr int W = kWavesSplit<T>;
+    return mega ? trace_paths_items<T, W, CAMQ, true> : trace_paths_items<T, W, CAMQ, false>;
 }
 constexpr uint64_t kScratchBudget = 24ull << 30;   // scratch (and record buffer) bytes a launch may ask for
 
@@ -675,6 +732,133 @@ static int launch_window(rt_context* c, const FrameArgs& a, const SessionWindow&
     return RT_OK;
 }
 
+// ---- per-pixel counts (rt_progressive_extend_map_async and its kin; DESIGN.md §4 "Per-pixel counts") ----
+// The pixels of one reduction that share a sample count: list[first .. first + n) of the reduction's index list.
+struct CountClass {
+    uint32_t spp, first, n;
+};
+static_assert(sizeof(MapItem) == kMapItemWords * sizeof(uint32_t), "the plan's records are the kernel's");
+constexpr size_t kMaxCountClasses = 256;   // distinct counts one reduction may have (a launch each)
+
+// Group the pixels by counts[p] (0: the pixel is left out): the classes in ascending count, and, with list, each
+// class's pixel indices in pixel order.  false: more than kMaxCountClasses distinct counts.
+static bool group_by_count(const uint32_t* counts, uint32_t n_pix, uint32_t* list, std::vector<CountClass>& cls) {
+    cls.clear();
+    auto find = [&](uint32_t n) {
+        return std::lower_bound(cls.begin(), cls.end(), n, [](const CountClass& k, uint32_t v) { return k.spp < v; });
+    };
+    size_t last = 0;   // the class of the previous pixel: neighbours mostly share a count
+    for (uint32_t p = 0; p < n_pix; ++p) {
+        if (counts[p] == 0u) continue;
+        if (last >= cls.size() || cls[last].spp != counts[p]) {
+            auto it = find(counts[p]);
+            if (it == cls.end() || it->spp != counts[p]) {
+                if (cls.size() == kMaxCountClasses) return false;
+                it = cls.insert(it, CountClass{counts[p], 0u, 0u});
+            }
+            last = (size_t)(it - cls.begin());
+        }
+        ++cls[last].n;
+    }
+    uint32_t at = 0;
+    for (CountClass& k : cls) { k.first = at; at += k.n; }
+    if (!list) return true;
+    for (CountClass& k : cls) k.n = 0u;
+    for (uint32_t p = 0; p < n_pix; ++p) {
+        if (counts[p] == 0u) continue;
+        if (cls[last].spp != counts[p]) last = (size_t)(find(counts[p]) - cls.begin());
+        CountClass& k = cls[last];
+        list[k.first + k.n] = p;
+        ++k.n;
+    }
+    return true;
+}
+
+// The session's frame at `spp` samples with the given outputs.
+static FrameArgs session_frame(const rt_context::Session& s, uint32_t spp, void* rgb, void* lin) {
+    return FrameArgs{&s.cam, s.depth, spp, s.seed, s.flags, s.rg, rgb, lin};
+}
+
+// Send the first `bytes` of the session's staging buffer to its device tables, on st.
+static int send_tables(rt_context::Session& s, size_t bytes, hipStream_t st) {
+    const int rc = ensure_bytes(s.tables, bytes, st);
+    if (rc != RT_OK) return rc;
+    HIPCHK(hipMemcpyAsync(s.tables.p, s.stage.p, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(s.stage.ev, st));
+    s.stage.pending = true;
+    return RT_OK;
+}
+
+// trace_paths_items over the n_items records at `items` (device), item_spp samples each on average.
+template <typename T>
+static int launch_items(rt_context* c, const rt_context::Session& s, const MapItem* items, uint32_t n_items,
+                        uint32_t item_spp, hipStream_t st) {
+    KParams<T> p;
+    bool camq = false;
+    int rc = frame_setup(c, session_frame(s, s.cap, nullptr, nullptr), 1u, st, p, camq);
+    if (rc != RT_OK) return rc;
+    const SplitPick<T> pick = camq ? pick_split<T, true>(p.n_mg > 0) : pick_split<T, false>(p.n_mg > 0);
+    void (*const ifn)(IParams<T>) = camq ? pick_items<T, true>(p.n_mg > 0) : pick_items<T, false>(p.n_mg > 0);
+    p.n_items = n_items;
+    uint64_t nblocks = 0;
+    rc = plan_grid(c, (const void*)ifn, pick.W, pick.id | kKernelItemsBit, n_items, item_spp, nblocks, p.blk_g);
+    if (rc != RT_OK) return rc;
+    // the records' strides are the capacity's (frame_setup laid the frame out for s.cap); the trace kernels read
+    // no sample count from the arguments: every item carries its own
+    IParams<T> ip;
+    memset(&ip, 0, sizeof(ip));
+    ip.w.s.k = p;
+    ip.w.s.rec = (char*)s.rec;
+    ip.w.s.n_pix = s.rg.row_count * s.rg.col_count;
+    ip.w.P_cap = p.P;
+    ip.items = items;
+    if ((rc = zero_claim_counters(c, st)) != RT_OK) return rc;
+    hipLaunchKernelGGL(ifn, dim3((uint32_t)nblocks), dim3(256), 0, st, ip);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// finish_window_list once per class, over the classes' index lists at `list` (device).  set_id: no trace kernel
+// ran in this call, so the kernel id is the session's sample-parallel kernels' without RT_KERNEL_ITEMS.
+template <typename T>
+static int launch_classes(rt_context* c, const rt_context::Session& s, const std::vector<CountClass>& cls,
+                          const uint32_t* list, void* rgb, void* lin, bool set_id, hipStream_t st) {
+    const uint32_t P_cap = prog_positions(s.cap);
+    // the scratch (one position map per wave) for the largest class, before the first launch reads it
+    uint64_t need = 0;
+    for (const CountClass& k : cls) {
+        const uint32_t P = prog_positions(k.spp), vb = paths_vbytes(P, paths_wide(P, s.depth), false);
+        uint64_t fb = std::min<uint64_t>(((uint64_t)k.n + 3) / 4, (uint64_t)c->n_cu * 8u);
+        fb = std::max<uint64_t>(1u, std::min<uint64_t>(fb, kScratchBudget / (4ull * vb)));
+        need = std::max<uint64_t>(need, (uint64_t)vb * fb * 4u);
+    }
+    int rc = ensure_bytes(c->scratch, need, st);
+    if (rc != RT_OK) return rc;
+    for (const CountClass& k : cls) {
+        KParams<T> p;
+        bool camq = false;
+        if ((rc = frame_setup(c, session_frame(s, k.spp, rgb, lin), 1u, st, p, camq)) != RT_OK) return rc;
+        if (set_id) {
+            const SplitPick<T> pick = camq ? pick_split<T, true>(p.n_mg > 0) : pick_split<T, false>(p.n_mg > 0);
+            void (*const wfn)(WParams<T>) = camq ? pick_window<T, true>(p.n_mg > 0) : pick_window<T, false>(p.n_mg > 0);
+            uint64_t nb = 0;
+            uint32_t g = 0;
+            if ((rc = plan_grid(c, (const void*)wfn, pick.W, pick.id, p.n_items, 1u, nb, g)) != RT_OK) return rc;
+            set_id = false;
+        }
+        p.sbytes = paths_sbytes(P_cap, sizeof(T), p.swide);   // a region's size: the capacity's (launch_window)
+        LParams<T> lp;
+        memset(&lp, 0, sizeof(lp));
+        uint64_t fblocks = 0;
+        if ((rc = split_params(c, p, (char*)s.rec, 1u, 1u, k.n, st, lp.w.s, fblocks)) != RT_OK) return rc;
+        lp.w.P_cap = P_cap;
+        lp.list = list + k.first;
+        hipLaunchKernelGGL(finish_window_list<T>, dim3((uint32_t)fblocks), dim3(256), 0, st, lp);
+        HIPCHK(hipGetLastError());
+    }
+    return RT_OK;
+}
+
 // The checks rt_render*_async and rt_progressive_begin share, after their own of the arguments: the flags
 // (live_only: a path that has the live kernels only), the sample and bounce limits, the image and the tile
 // range, which *rg receives (range == NULL: the whole image).  count_name: what the entry point calls spp.
@@ -831,40 +1015,239 @@ extern "C" int rt_progressive_begin(rt_context* c, const rt_camera* cam, uint32_
     s.seed = seed;
     s.rec = rec;
     s.bytes = bytes;
+    s.done.assign((size_t)n_pix, 0u);
     return RT_OK;
 }
 
-extern "C" int rt_progressive_extend_async(rt_context* c, uint32_t spp_total, void* d_rgb8, void* d_linear, void* stream) {
-    const std::string who = "rt_progressive_extend_async";
-    if (!c) return fail(RT_ERR_INVALID, who + ": NULL context");
+// An extend of a session whose pixels all hold s.done_min samples, to spp_total for every pixel:
+// rt_progressive_extend_async, and a map that is uniform.
+static int extend_uniform(rt_context* c, const std::string& who, uint32_t spp_total, void* d_rgb8, void* d_linear,
+                          void* stream) {
     rt_context::Session& s = c->prog;
-    if (!s.open) return fail(RT_ERR_INVALID, who + ": no session open on this context");
+    const uint32_t done = s.done_min;
     if (spp_total == 0) return fail(RT_ERR_INVALID, who + ": spp_total == 0");
-    if (spp_total < s.done) return fail(RT_ERR_INVALID, who + ": spp_total below the samples already traced");
+    if (spp_total < done) return fail(RT_ERR_INVALID, who + ": spp_total below the samples already traced");
     if (spp_total > s.cap) return fail(RT_ERR_INVALID, who + ": spp_total above the session's spp_capacity");
     const bool f32 = (s.flags & RT_FLAG_F32) != 0;
     const uint64_t n_pix = (uint64_t)s.rg.row_count * s.rg.col_count;
-    SessionWindow w{(char*)s.rec, s.cap, s.done, s.done, 1u, 1u, spp_total > s.done, d_rgb8 != nullptr || d_linear != nullptr};
+    SessionWindow w{(char*)s.rec, s.cap, done, done, 1u, 1u, spp_total > done, d_rgb8 != nullptr || d_linear != nullptr};
     if (!w.trace && !w.finish) return RT_OK;
     if (w.trace) {
         const uint32_t waves = (uint32_t)c->n_cu * 4u * (uint32_t)(f32 ? kWavesSplit<float> : kWavesSplit<double>);
         ProgWindow pw;
-        const int prc = progressive_window(n_pix, s.done, spp_total, waves, &pw);
+        const int prc = progressive_window(n_pix, done, spp_total, waves, &pw);
         if (prc != kPlanOk) return fail(prc, who + ": no plan for this window (more than 0x7FFFFFFF work items)");
         w.S = pw.S;
         w.nsub = pw.nsub;
         w.s_base = pw.base;
     }
-    const FrameArgs a{&s.cam, s.depth, spp_total, s.seed, s.flags, s.rg, d_rgb8, d_linear};
+    const FrameArgs a = session_frame(s, spp_total, d_rgb8, d_linear);
     hipStream_t st = (hipStream_t)stream;
     int rc = begin_launch(c, st);   // the session shares the counter, scratch and camera tables
     if (rc != RT_OK) return rc;
     rc = f32 ? launch_window<float>(c, a, w, st) : launch_window<double>(c, a, w, st);
     if (rc != RT_OK) return rc;
-    if ((rc = end_launch(c, st, n_pix, n_pix * (uint64_t)(spp_total - s.done))) != RT_OK) return rc;
-    s.done = spp_total;
+    if ((rc = end_launch(c, st, n_pix, n_pix * (uint64_t)(spp_total - done))) != RT_OK) return rc;
+    s.set_done(spp_total);
     s.stream = st;
     s.have_stream = true;
+    return RT_OK;
+}
+
+// One reduction of a call over per-pixel counts: the pixels with counts[p] > 0, each at its count, into the outputs.
+struct MapReduce {
+    const uint32_t* counts;
+    void* rgb;
+    void* lin;
+};
+
+// The work of the per-pixel-count calls.  Traces [s.done[p], target[p]) of every pixel (target == NULL: nothing),
+// then runs the n_red reductions in order; `extra` (n_extra words, may be NULL) is sent to the device behind the
+// other tables and *d_extra receives its device address.  The callers have checked the arrays.  Returns with
+// *enqueued false when there was nothing to do.
+static int run_map(rt_context* c, const std::string& who, const uint32_t* target, const MapReduce* red, size_t n_red,
+                   const uint32_t* extra, size_t n_extra, const uint32_t** d_extra, hipStream_t st, bool* enqueued) {
+    rt_context::Session& s = c->prog;
+    const bool f32 = (s.flags & RT_FLAG_F32) != 0;
+    const uint32_t n_pix = s.rg.row_count * s.rg.col_count;
+    const uint32_t waves = (uint32_t)c->n_cu * 4u * (uint32_t)(f32 ? kWavesSplit<float> : kWavesSplit<double>);
+    *enqueued = false;
+    uint32_t S = 0;
+    uint64_t n_items = 0, traced = 0;
+    if (target) {
+        const int prc = progressive_map_plan(n_pix, s.done.data(), target, waves, &S, &n_items, nullptr, 0u);
+        if (prc != kPlanOk) return fail(prc, who + ": no plan for this map (more than 0x7FFFFFFF work items)");
+        for (uint32_t p = 0; p < n_pix; ++p) traced += target[p] - s.done[p];
+    }
+    std::vector<std::vector<CountClass>> cls(n_red);
+    size_t list_words = 0;
+    for (size_t r = 0; r < n_red; ++r) {
+        if (!group_by_count(red[r].counts, n_pix, nullptr, cls[r]))
+            return fail(RT_ERR_UNSUPPORTED, who + ": more than 256 distinct sample counts in one reduction");
+        if (!cls[r].empty()) list_words += n_pix;
+    }
+    if (n_items == 0 && list_words == 0) return RT_OK;
+    // the tables, in one copy: the items' records, the reductions' index lists, the caller's words.  The host
+    // fills them before the launch begins, so that the collect's kernel_ms is the device's time alone
+    HIPCHK(hipSetDevice(c->device));
+    const size_t item_words = (size_t)n_items * kMapItemWords, words = item_words + list_words + n_extra;
+    int rc = stage_reserve(s.stage, words * sizeof(uint32_t));
+    if (rc != RT_OK) return rc;
+    uint32_t* const tab = (uint32_t*)s.stage.p;
+    if (n_items && progressive_map_plan(n_pix, s.done.data(), target, waves, &S, &n_items, tab, n_items) != kPlanOk)
+        return fail(RT_ERR_INVALID, who + ": internal: the plan's two passes disagree");
+    size_t at = item_words;
+    std::vector<size_t> list_at(n_red, 0);
+    for (size_t r = 0; r < n_red; ++r) {
+        if (cls[r].empty()) continue;
+        (void)group_by_count(red[r].counts, n_pix, tab + at, cls[r]);
+        list_at[r] = at;
+        at += n_pix;
+    }
+    if (n_extra) memcpy(tab + at, extra, n_extra * sizeof(uint32_t));
+    if ((rc = begin_launch(c, st)) != RT_OK) return rc;   // the session shares the counter, scratch and camera tables
+    if ((rc = send_tables(s, words * sizeof(uint32_t), st)) != RT_OK) return rc;
+    const uint32_t* const d_tab = (const uint32_t*)s.tables.p;
+    if (d_extra) *d_extra = d_tab + at;
+    if (n_items) {
+        const uint32_t item_spp = (uint32_t)std::max<uint64_t>(1u, traced / n_items);   // the mean item
+        rc = f32 ? launch_items<float>(c, s, (const MapItem*)d_tab, (uint32_t)n_items, item_spp, st)
+                 : launch_items<double>(c, s, (const MapItem*)d_tab, (uint32_t)n_items, item_spp, st);
+        if (rc != RT_OK) return rc;
+    }
+    bool set_id = n_items == 0;
+    for (size_t r = 0; r < n_red; ++r) {
+        if (cls[r].empty()) continue;
+        rc = f32 ? launch_classes<float>(c, s, cls[r], d_tab + list_at[r], red[r].rgb, red[r].lin, set_id, st)
+                 : launch_classes<double>(c, s, cls[r], d_tab + list_at[r], red[r].rgb, red[r].lin, set_id, st);
+        if (rc != RT_OK) return rc;
+        set_id = false;
+    }
+    if (target) {
+        s.done.assign(target, target + n_pix);
+        s.done_min = *std::min_element(s.done.begin(), s.done.end());
+        s.done_max = *std::max_element(s.done.begin(), s.done.end());
+    }
+    s.stream = st;
+    s.have_stream = true;
+    *enqueued = true;
+    return end_launch(c, st, n_pix, traced);
+}
+
+static int open_session(rt_context* c, const std::string& who) {
+    if (!c) return fail(RT_ERR_INVALID, who + ": NULL context");
+    if (!c->prog.open) return fail(RT_ERR_INVALID, who + ": no session open on this context");
+    return RT_OK;
+}
+
+extern "C" int rt_progressive_extend_async(rt_context* c, uint32_t spp_total, void* d_rgb8, void* d_linear, void* stream) {
+    const std::string who = "rt_progressive_extend_async";
+    int rc = open_session(c, who);
+    if (rc != RT_OK) return rc;
+    rt_context::Session& s = c->prog;
+    if (s.done_min == s.done_max) return extend_uniform(c, who, spp_total, d_rgb8, d_linear, stream);
+    // after a non-uniform map: every pixel goes from its own count to spp_total
+    if (spp_total < s.done_max) return fail(RT_ERR_INVALID, who + ": spp_total below the samples a pixel already holds");
+    if (spp_total > s.cap) return fail(RT_ERR_INVALID, who + ": spp_total above the session's spp_capacity");
+    const std::vector<uint32_t> target(s.done.size(), spp_total);
+    const MapReduce red{target.data(), d_rgb8, d_linear};
+    bool enqueued = false;
+    return run_map(c, who, target.data(), &red, d_rgb8 || d_linear ? 1u : 0u, nullptr, 0u, nullptr, (hipStream_t)stream,
+                   &enqueued);
+}
+
+extern "C" int rt_progressive_extend_map_async(rt_context* c, const uint32_t* spp_target, void* d_rgb8, void* d_linear,
+                                               void* stream) {
+    const std::string who = "rt_progressive_extend_map_async";
+    int rc = open_session(c, who);
+    if (rc != RT_OK) return rc;
+    rt_context::Session& s = c->prog;
+    if (!spp_target) return fail(RT_ERR_INVALID, who + ": spp_target is NULL");
+    const bool out = d_rgb8 != nullptr || d_linear != nullptr;
+    bool same = s.done_min == s.done_max;
+    for (size_t p = 0; p < s.done.size(); ++p) {
+        const uint32_t t = spp_target[p];
+        if (t < s.done[p]) return fail(RT_ERR_INVALID, who + ": a target below the samples its pixel already holds");
+        if (t > s.cap) return fail(RT_ERR_INVALID, who + ": a target above the session's spp_capacity");
+        if (t == 0u && out) return fail(RT_ERR_INVALID, who + ": a target of 0 with an output (no image of 0 samples)");
+        same = same && t == spp_target[0];
+    }
+    if (same)   // a uniform map is rt_progressive_extend_async: same kernels, same stats
+        return spp_target[0] == 0u ? RT_OK : extend_uniform(c, who, spp_target[0], d_rgb8, d_linear, stream);
+    const MapReduce red{spp_target, d_rgb8, d_linear};
+    bool enqueued = false;
+    return run_map(c, who, spp_target, &red, out ? 1u : 0u, nullptr, 0u, nullptr, (hipStream_t)stream, &enqueued);
+}
+
+extern "C" int rt_progressive_snapshot_map_async(rt_context* c, const uint32_t* spp_count, void* d_rgb8, void* d_linear,
+                                                 void* stream) {
+    const std::string who = "rt_progressive_snapshot_map_async";
+    int rc = open_session(c, who);
+    if (rc != RT_OK) return rc;
+    rt_context::Session& s = c->prog;
+    if (!d_rgb8 && !d_linear) return fail(RT_ERR_INVALID, who + ": both outputs are NULL");
+    const uint32_t* counts = spp_count ? spp_count : s.done.data();
+    for (size_t p = 0; p < s.done.size(); ++p)
+        if (counts[p] == 0u || counts[p] > s.done[p])
+            return fail(RT_ERR_INVALID, who + ": a count of 0 or above the samples its pixel holds");
+    const MapReduce red{counts, d_rgb8, d_linear};
+    bool enqueued = false;
+    return run_map(c, who, nullptr, &red, 1u, nullptr, 0u, nullptr, (hipStream_t)stream, &enqueued);
+}
+
+extern "C" int rt_progressive_counts(rt_context* c, uint32_t* out) {
+    const std::string who = "rt_progressive_counts";
+    const int rc = open_session(c, who);
+    if (rc != RT_OK) return rc;
+    if (!out) return fail(RT_ERR_INVALID, who + ": out is NULL");
+    std::copy(c->prog.done.begin(), c->prog.done.end(), out);
+    return RT_OK;
+}
+
+extern "C" int rt_progressive_error_async(rt_context* c, void* d_error, void* stream) {
+    const std::string who = "rt_progressive_error_async";
+    int rc = open_session(c, who);
+    if (rc != RT_OK) return rc;
+    rt_context::Session& s = c->prog;
+    if (!d_error) return fail(RT_ERR_INVALID, who + ": d_error is NULL");
+    const uint32_t n_pix = (uint32_t)s.done.size();
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t lin_bytes = (size_t)n_pix * 3u * sizeof(double);
+    if ((rc = ensure_bytes(s.lin_full, lin_bytes, st)) != RT_OK) return rc;
+    if ((rc = ensure_bytes(s.lin_half, lin_bytes, st)) != RT_OK) return rc;
+    // the snapshot at half the count, then at the count; a pixel below 2 samples has no half (0: left out) and
+    // reads +inf, whatever its buffers hold
+    std::vector<uint32_t> half(s.done);
+    for (uint32_t& n : half) n /= 2u;
+    const MapReduce red[2] = {{half.data(), nullptr, s.lin_half.p}, {s.done.data(), nullptr, s.lin_full.p}};
+    const uint32_t* d_counts = nullptr;
+    bool enqueued = false;
+    if ((rc = run_map(c, who, nullptr, red, 2u, s.done.data(), n_pix, &d_counts, st, &enqueued)) != RT_OK) return rc;
+    if (!enqueued) {   // no pixel holds a sample: every estimate is +inf, and the counts have not gone up
+        if ((rc = begin_launch(c, st)) != RT_OK) return rc;
+        if ((rc = stage_reserve(s.stage, (size_t)n_pix * sizeof(uint32_t))) != RT_OK) return rc;
+        memcpy(s.stage.p, s.done.data(), (size_t)n_pix * sizeof(uint32_t));
+        if ((rc = send_tables(s, (size_t)n_pix * sizeof(uint32_t), st)) != RT_OK) return rc;
+        d_counts = (const uint32_t*)s.tables.p;
+        s.stream = st;
+        s.have_stream = true;
+    }
+    hipLaunchKernelGGL(progressive_error, dim3((n_pix + 255u) / 256u), dim3(256), 0, st, (const double*)s.lin_full.p,
+                       (const double*)s.lin_half.p, d_counts, (double*)d_error, n_pix);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_last, st));   // kernel_ms covers the estimate's kernel as well
+    return RT_OK;
+}
+
+extern "C" int rt_progressive_map_plan(uint64_t n_pixels, const uint32_t* done, const uint32_t* target,
+                                       uint32_t resident_waves, uint32_t* samples_per_item, uint64_t* n_items,
+                                       uint32_t* items, uint64_t items_capacity) {
+    const int rc = progressive_map_plan(n_pixels, done, target, resident_waves, samples_per_item, n_items, items,
+                                        items_capacity);
+    if (rc != kPlanOk)
+        return fail(rc, "rt_progressive_map_plan: a NULL array or output, no pixels, a target below done, too small an "
+                        "item capacity (invalid); a target above 2^20, more than 0x7FFFFFFF pixels or items (unsupported)");
     return RT_OK;
 }
 

@@ -1,7 +1,7 @@
 // rt_progressive_plan.hpp — the host arithmetic of a progressive session (rt_progressive_*): the record
 // buffer a session of a given sample capacity needs, and how one extend's sample window [done, spp_total)
-// is dealt into work items.  Pure host C++ (no HIP): the library and the stand-alone sanitizer program
-// tests/sanitize/progressive_plan_san.cpp include it.
+// is dealt into work items, uniformly or with a sample count per pixel.  Pure host C++ (no HIP): the library and
+// the stand-alone sanitizer programs tests/sanitize/progressive_plan_san.cpp and map_plan_san.cpp include it.
 #pragma once
 #include <stdint.h>
 
@@ -79,6 +79,72 @@ inline int progressive_window(uint64_t n_pixels, uint32_t done, uint32_t spp_tot
     const int rc = split_plan(n_pixels, spp_total - done, resident_waves, &S, &n);
     if (rc != kPlanOk) return rc;
     return progressive_window_s(n_pixels, done, spp_total, S, w);
+}
+
+// ---- per-pixel counts (rt_progressive_extend_map_async) ----
+// One extend of a map: pixel p goes from done[p] to target[p] samples.  The items are records of four words
+// {pixel, first, end, 0} (the item table trace_paths_items reads), in pixel order with a pixel's items adjacent.
+constexpr uint32_t kMapItemWords = 4;
+
+// The plan: with A the active pixels (target > done) and mean = ceil(sum of (target - done) / A), S is
+// split_plan(A, mean, resident_waves)'s.  Where S is a multiple of kSplitGrain, pixel p's items are those of
+// progressive_window_s(1, done[p], target[p], S): they lie on the grid base_p + j S, base_p = done[p] rounded down
+// to the grain, so no two items of a launch share a 128-byte line of a pixel's u8 e array.  Any other S (the
+// one-item-per-pixel plan at a mean off the grain) makes every active pixel one item [done[p], target[p]).  A
+// uniform map therefore has the items of progressive_window.
+// *samples_per_item: S (0: no pixel is active); *n_items: the items of the plan, always set when the arrays are
+// valid.  items (may be NULL: count only) receives them when items_capacity (in items) holds them all.
+// Invalid: a NULL array or output, no pixels, a target below done, items given with too small a capacity.
+// Unsupported: a target above 2^20, more than 0x7FFFFFFF pixels or items.
+inline int progressive_map_plan(uint64_t n_pixels, const uint32_t* done, const uint32_t* target,
+                                uint32_t resident_waves, uint32_t* samples_per_item, uint64_t* n_items,
+                                uint32_t* items, uint64_t items_capacity) {
+    if (!samples_per_item || !n_items) return kPlanInvalid;
+    *samples_per_item = 0;
+    *n_items = 0;
+    if (!done || !target || n_pixels == 0) return kPlanInvalid;
+    if (n_pixels > kSplitMaxItems) return kPlanUnsupported;
+    uint64_t active = 0, total = 0;
+    for (uint64_t p = 0; p < n_pixels; ++p) {
+        if (target[p] < done[p]) return kPlanInvalid;
+        if (target[p] > kSplitMaxSpp) return kPlanUnsupported;
+        if (target[p] > done[p]) { ++active; total += target[p] - done[p]; }   // < 2^31 x 2^20
+    }
+    if (active == 0) return kPlanOk;
+    const uint32_t mean = (uint32_t)((total + active - 1u) / active);
+    uint32_t S = 0;
+    uint64_t n = 0;
+    const int rc = split_plan(active, mean, resident_waves, &S, &n);
+    if (rc != kPlanOk) return rc;
+    const bool grid = S % kSplitGrain == 0u;
+    uint64_t count = 0;
+    for (uint64_t p = 0; p < n_pixels; ++p) {
+        if (target[p] <= done[p]) continue;
+        const uint32_t base = grid ? done[p] - done[p] % kSplitGrain : done[p];
+        count += grid ? split_nsub(target[p] - base, S) : 1u;   // < 2^31 x 2^13
+    }
+    if (count > kSplitMaxItems) return kPlanUnsupported;
+    *samples_per_item = S;
+    *n_items = count;
+    if (!items) return kPlanOk;
+    if (items_capacity < count) return kPlanInvalid;
+    uint32_t* it = items;
+    for (uint64_t p = 0; p < n_pixels; ++p) {
+        if (target[p] <= done[p]) continue;
+        if (!grid) {
+            it[0] = (uint32_t)p; it[1] = done[p]; it[2] = target[p]; it[3] = 0u;
+            it += kMapItemWords;
+            continue;
+        }
+        ProgWindow w;
+        (void)progressive_window_s(1u, done[p], target[p], S, &w);   // valid: checked above
+        for (uint32_t j = 0; j < w.nsub; ++j, it += kMapItemWords) {
+            it[0] = (uint32_t)p;
+            prog_item(w, done[p], target[p], j, &it[1], &it[2]);
+            it[3] = 0u;
+        }
+    }
+    return kPlanOk;
 }
 
 }  // namespace rt

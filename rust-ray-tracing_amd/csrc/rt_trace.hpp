@@ -89,7 +89,7 @@ template <typename T, bool B> constexpr bool kSplitKernel = B;
 
 template <typename T, int W, bool ROOT2, int MODE = kModeV2, bool CAMQ = false, bool MEGA = false>
 __global__ __launch_bounds__(256, W) void trace_paths(KParams<T> p) {
-    constexpr bool SPLIT = kSplitKernel<T, false>, WIN = kSplitKernel<T, false>;
+    constexpr bool SPLIT = kSplitKernel<T, false>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, false>;
 #include "rt_trace_body.hpp"
 }
 
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256, W) void trace_paths(KParams<T> p) {
 // over (pixel, sample sub-range) items; finish_records follows it on the same stream.
 template <typename T, int W, bool CAMQ, bool MEGA>
 __global__ __launch_bounds__(256, W) void trace_paths_split(SParams<T> sp) {
-    constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, false>, ROOT2 = false;
+    constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, false>, ROOT2 = false;
     constexpr int MODE = kModeV2;
     const KParams<T>& p = sp.k;
 #include "rt_trace_body.hpp"
@@ -108,9 +108,21 @@ __global__ __launch_bounds__(256, W) void trace_paths_split(SParams<T> sp) {
 // (WParams).  Kernels of their own beside trace_paths_split, whose code, names and arguments stay as they were.
 template <typename T, int W, bool CAMQ, bool MEGA>
 __global__ __launch_bounds__(256, W) void trace_paths_window(WParams<T> wp) {
-    constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, true>, ROOT2 = false;
+    constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, true>, ITEMS = kSplitKernel<T, false>, ROOT2 = false;
     constexpr int MODE = kModeV2;
     const KParams<T>& p = wp.s.k;
+#include "rt_trace_body.hpp"
+}
+
+// A session's tracing kernel over per-pixel sample counts (rt_progressive_extend_map_async): trace_paths_split
+// with ITEMS.  A claimed item is a record {pixel, first, end} of the item table, so every pixel has its own
+// window; the claim scheme and the records are trace_paths_window's.  A kernel of its own beside
+// trace_paths_window, whose code, name and arguments stay as they were.
+template <typename T, int W, bool CAMQ, bool MEGA>
+__global__ __launch_bounds__(256, W) void trace_paths_items(IParams<T> ip) {
+    constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, true>, ROOT2 = false;
+    constexpr int MODE = kModeV2;
+    const KParams<T>& p = ip.w.s.k;
 #include "rt_trace_body.hpp"
 }
 
@@ -162,6 +174,47 @@ __global__ __launch_bounds__(256) void finish_window(WParams<T> wp) {
         __builtin_amdgcn_wave_barrier();
     }
     if (lane == 0 && iters != 0ull) atomicAdd(&q.k.segs[(gw & (kSegShards - 1)) * kSegStride + 2], iters);
+}
+
+// finish_window over an index list: the pixels of a session that are reduced at the same count (the counts in
+// the KParams, as finish_window reads them), one launch per distinct count of a per-pixel map.  px = list[i];
+// the region and the output element are pixel px's.
+template <typename T>
+__global__ __launch_bounds__(256) void finish_window_list(LParams<T> lp) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][64];
+    __shared__ __attribute__((aligned(16))) T s_stage[4][3][64];
+    __shared__ __attribute__((aligned(16))) uint16_t s_lmap[4][kLMapCap > 0u ? kLMapCap : 2];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const auto& q = *cold_split_args<T>();
+    const uint32_t gw = blockIdx.x * 4u + wave, nw = gridDim.x * 4u;
+    const RScratch<T> sc{q.k.scratch + (size_t)gw * q.k.scratch_stride, q.rec, cold_window_args<T>()->P_cap, q.k.sbytes,
+                         q.k.swide};
+    const uint32_t n_list = q.n_pix;
+    const cptr<uint32_t> list = (cptr<uint32_t>)cold_list_args<T>()->list;
+    unsigned long long iters = 0;
+    for (uint64_t i = gw; i < n_list; i += nw) {
+        const uint32_t px = list[i];
+        iters += finish_pixel<T, kModeV2, true>(sc, px, px, s_hist[wave], s_stage[wave],
+                                                kLMapCap > 0u ? s_lmap[wave] : nullptr, false);
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (lane == 0 && iters != 0ull) atomicAdd(&q.k.segs[(gw & (kSegShards - 1)) * kSegStride + 2], iters);
+}
+
+// A session's error estimate (rt_progressive_error_async): per pixel the largest channel difference between the
+// linear snapshot at its count and at half its count, both already in device memory as doubles; +inf below 2
+// samples.
+__global__ __launch_bounds__(256) void progressive_error(const double* full, const double* half,
+                                                         const uint32_t* counts, double* out, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    double e = __builtin_huge_val();
+    if (counts[i] >= 2u) {
+        e = 0.0;
+        for (uint32_t ch = 0; ch < 3u; ++ch) e = fmax(e, fabs(full[3u * i + ch] - half[3u * i + ch]));
+    }
+    out[i] = e;
 }
 
 }  // namespace rt

@@ -1,9 +1,10 @@
 // rt_trace_body.hpp -- the statements of the persistent path-regeneration kernel, included as the body of
 // trace_paths and of trace_paths_split (rt_trace.hpp; not a header on its own).  In scope: T, W, ROOT2, MODE,
-// CAMQ, MEGA, SPLIT, WIN (SPLIT only: the items tile a sample window, WParams<T>) and the kernel arguments p
-// (KParams<T>).
+// CAMQ, MEGA, SPLIT, WIN (SPLIT only: the items tile a sample window, WParams<T>), ITEMS (SPLIT only: the items
+// are read from a table, IParams<T>) and the kernel arguments p (KParams<T>).
     constexpr bool SC = MODE == kModeScalar;
     static_assert(!SPLIT || (MODE == kModeV2 && !ROOT2), "the sample-parallel kernels cover the live path only");
+    static_assert(!ITEMS || (SPLIT && !WIN), "an item table replaces the window's decode");
     // fp64 at 5+ waves per SIMD: a 64-entry queue (half the LDS), so the parked ray fits in 32 KB per
     // workgroup
     constexpr bool kF64Park = sizeof(T) == 8 && W >= 5;
@@ -176,7 +177,12 @@
                 }
                 const uint32_t s = __builtin_ctz(avail);
                 uint32_t first = 0;
-                if constexpr (SPLIT) {   // item -> (pixel, samples [first, cur_end))
+                if constexpr (ITEMS) {   // item -> its 16-byte record {pixel, first, end}: wave-uniform scalar loads
+                    const cptr<MapItem> tab = (cptr<MapItem>)__builtin_assume_aligned(cold_items_args<T>()->items, 16);
+                    first = tab[item].first;
+                    cur_end = tab[item].end;
+                    item = tab[item].pixel;
+                } else if constexpr (SPLIT) {   // item -> (pixel, samples [first, cur_end))
                     const auto& sq = *cold_split_args<T>();
                     const uint32_t px = item / sq.nsub;
                     first = (item - px * sq.nsub) * sq.S;

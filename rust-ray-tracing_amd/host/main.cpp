@@ -3,7 +3,7 @@
 //   rt-render [--scene scene.toml] [--width 3840] [--height 2160] [--spp 100] [--bounces 50]
 //             [--seed 0x5EED0001] [--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar]
 //             [--out output.png|.ppm] [--block-size B] [--sample-parallel] [--progressive n1,n2,...]
-//             [--dump-scene]
+//             [--adaptive TOL --spp-min N [--count-map counts.png|.ppm]] [--dump-scene]
 //
 // --mode picks which of the reference's renderers is reproduced (include/rt_mi355x.h): the live
 // render_vectorized2 (default), render_vectorized, or the scalar render.
@@ -13,6 +13,11 @@
 // increasing, all below --spp) it writes <out stem>_spp<count, 7 digits><ext> and prints one line with the
 // count, the kernel time so far and the sample rate; only the new samples of a step are traced.  At --spp it
 // writes --out, byte for byte the file the same command writes without --progressive.  The live path only.
+// --adaptive TOL --spp-min N samples adaptively in one progressive session (rt_progressive_extend_map_async):
+// every pixel gets N samples, then the pixels whose error estimate (the largest channel difference between the
+// pixel at its count and at half its count) is above TOL double their count, up to --spp, until none is left.
+// It prints per step the active pixels and the samples traced, and at the end the total and its share of
+// pixels x spp.  --count-map PATH writes each pixel's count as grey RGB8, 255 * count / spp.  The live path only.
 //
 // Defaults are main.rs's hard-coded values (scene.toml in the working directory, 3840x2160, 50
 // bounces, 100 spp, camera from (16,2,18.5) looking at the origin, vfov 30, focal 10, no defocus,
@@ -77,8 +82,10 @@ int main(int argc, char** argv) {
     uint32_t width = 3840, height = 2160, spp = 100, bounces = 50, flags = 0, block_size = 0;
     uint64_t seed = 0x5EED0001ull;
     bool dump = false, sample_parallel = false;
-    std::string progressive_arg;
-    bool progressive = false;
+    std::string progressive_arg, count_map;
+    bool progressive = false, adaptive = false;
+    double tolerance = 0.0;
+    uint32_t spp_min = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -105,11 +112,15 @@ int main(int argc, char** argv) {
         else if (a == "--block-size") block_size = (uint32_t)std::stoul(next());
         else if (a == "--sample-parallel") sample_parallel = true;
         else if (a == "--progressive") { progressive_arg = next(); progressive = true; }
+        else if (a == "--adaptive") { tolerance = std::stod(next()); adaptive = true; }
+        else if (a == "--spp-min") spp_min = (uint32_t)std::stoul(next());
+        else if (a == "--count-map") count_map = next();
         else if (a == "--dump-scene") dump = true;
         else if (a == "-h" || a == "--help") {
             std::puts("rt-render [--scene scene.toml] [--width W] [--height H] [--spp S] [--bounces B] [--seed N] "
                       "[--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar] [--out output.png] [--block-size B] "
-                      "[--sample-parallel] [--progressive n1,n2,...] [--dump-scene]");
+                      "[--sample-parallel] [--progressive n1,n2,...] [--adaptive TOL --spp-min N [--count-map PATH]] "
+                      "[--dump-scene]");
             return 0;
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -138,6 +149,23 @@ int main(int argc, char** argv) {
             counts.push_back(n);
         }
         if (counts.empty() || progressive_arg.back() == ',') return bad("expected n1,n2,...");
+    }
+    if (adaptive) {
+        auto bad = [](const std::string& why) {
+            std::fprintf(stderr, "--adaptive: %s\n", why.c_str());
+            return 2;
+        };
+        if (flags & RT_FLAG_ROOT2) return bad("not with --root2: a session's records are the live path's");
+        if (flags & (RT_FLAG_MODE_VECTORIZED | RT_FLAG_MODE_SCALAR | RT_FLAG_MODE_VECTORIZED3))
+            return bad("only with --mode vectorized2: a session's records are the live path's");
+        if (block_size != 0) return bad("not with --block-size: every step is one launch over the whole image");
+        if (progressive) return bad("not with --progressive: the error estimate picks the counts");
+        if (tolerance != tolerance) return bad("the tolerance is NaN");
+        if (spp_min < 1 || spp_min > spp)
+            return bad("--spp-min must be between 1 and --spp (" + std::to_string(spp) + "), the most a pixel gets");
+    } else if (spp_min != 0 || !count_map.empty()) {
+        std::fprintf(stderr, "--spp-min and --count-map go with --adaptive\n");
+        return 2;
     }
     try {
         std::ifstream in(scene_path, std::ios::binary);   // main.rs:31-34
@@ -177,9 +205,30 @@ int main(int argc, char** argv) {
                         range_err ? " (a pixel channel exceeded 2.0 at this count)" : "");
             std::fflush(stdout);
         };
-        auto [image, stat] = progressive ? renderer.render_progressive(bounces, spp, scene, camera, counts, step)
-                                         : renderer.render(bounces, spp, scene, camera);       // main.rs:64
+        std::vector<uint32_t> pixel_counts;   // --adaptive: the samples each pixel got
+        uint32_t steps = 0;
+        auto adaptive_step = [&](size_t active, uint64_t traced) {
+            std::printf("Adaptive: step %u, %zu active pixels, %llu samples traced\n", ++steps, active,
+                        (unsigned long long)traced);
+            std::fflush(stdout);
+        };
+        auto [image, stat] = adaptive ? renderer.render_adaptive(bounces, spp_min, spp, tolerance, scene, camera,
+                                                                 pixel_counts, adaptive_step)
+                             : progressive ? renderer.render_progressive(bounces, spp, scene, camera, counts, step)
+                                           : renderer.render(bounces, spp, scene, camera);     // main.rs:64
         save_image(out, image.width, image.height, image.data.data());                         // main.rs:66
+        if (adaptive) {
+            const double full = (double)image.width * image.height * spp;
+            std::printf("Adaptive: %u steps, %llu samples traced, %.1f %% of %u x %u x %u spp\n", steps,
+                        (unsigned long long)stat.gpu.samples, 100.0 * (double)stat.gpu.samples / full, image.width,
+                        image.height, spp);
+            if (!count_map.empty()) {
+                std::vector<uint8_t> grey(pixel_counts.size() * 3);
+                for (size_t p = 0; p < pixel_counts.size(); ++p)
+                    grey[3 * p] = grey[3 * p + 1] = grey[3 * p + 2] = (uint8_t)(255ull * pixel_counts[p] / spp);
+                save_image(count_map, image.width, image.height, grey.data());
+            }
+        }
         std::printf("Image Size: %u x %u\n", camera.image_width(), camera.image_height());    // main.rs:68-71
         std::printf("Total Pixels: %zu\n", stat.pixels_rendered);
         std::printf("Time Taken: %.3f seconds\n", stat.duration.count());

@@ -366,6 +366,84 @@ struct GpuRenderer : Renderer {
         return {std::move(img), stat};
     }
 
+    // Adaptive render (rt_progressive_extend_map_async and its kin; GpuRenderer.adaptive of the Python package,
+    // step for step): a session of capacity spp, every pixel to spp_min samples, then, while some pixel's error
+    // estimate (rt_progressive_error_async) is above `tolerance` and its count below spp, those pixels double
+    // their count (up to spp).  Pixel p of the image is render()'s at counts[p] samples.  step(active pixels,
+    // samples the step traced) is called after every refinement step.  The live path only.
+    template <typename Step>
+    std::pair<RgbImage, RenderStat> render_adaptive(size_t max_bounces, size_t spp_min, size_t spp, double tolerance,
+                                                    const Scene& scene, const Camera& camera,
+                                                    std::vector<uint32_t>& counts, Step&& step) {
+        const auto t0 = std::chrono::steady_clock::now();
+        FlatScene flat = scene.flatten();
+        rt_scene rs = flat.view();
+        RgbImage img{camera.image_width(), camera.image_height(), {}};
+        const size_t npx = (size_t)img.width * img.height;
+        img.data.resize(npx * 3);
+        struct Ctx {
+            rt_context* c = nullptr;
+            void* buf = nullptr;
+            void* err = nullptr;
+            ~Ctx() {   // destroy ends the session
+                if (buf) rt_device_free(c, buf);
+                if (err) rt_device_free(c, err);
+                if (c) rt_context_destroy(c);
+            }
+        } x;
+        auto chk = [](int rc, const char* what) {
+            if (rc != RT_OK) throw Panic(std::string(what) + ": " + rt_last_error());
+        };
+        chk(rt_context_create(0, &x.c), "rt_context_create");
+        chk(rt_context_set_scene(x.c, &rs), "rt_context_set_scene");
+        chk(rt_device_alloc(x.c, npx * 3, &x.buf), "rt_device_alloc");
+        chk(rt_device_alloc(x.c, npx * sizeof(double), &x.err), "rt_device_alloc");
+        chk(rt_progressive_begin(x.c, &camera.c, (uint32_t)max_bounces, (uint32_t)spp, seed, flags, nullptr, 0),
+            "rt_progressive_begin");
+        rt_stats total{};
+        auto collect = [&]() -> bool {   // true: RT_ERR_RANGE
+            rt_stats st{};
+            const int rc = rt_context_collect(x.c, nullptr, &st);
+            if (rc != RT_ERR_RANGE) chk(rc, "rt_context_collect");
+            total.kernel_ms += st.kernel_ms;
+            total.pixels = npx;
+            total.samples += st.samples;
+            total.ray_segments += st.ray_segments;
+            total.lane_slots += st.lane_slots;
+            total.bounce_iters += st.bounce_iters;
+            total.kernel_id = st.kernel_id;
+            total.kernel_wg_per_cu = st.kernel_wg_per_cu;
+            return rc == RT_ERR_RANGE;
+        };
+        chk(rt_progressive_extend_async(x.c, (uint32_t)spp_min, nullptr, nullptr, nullptr), "rt_progressive_extend_async");
+        (void)collect();
+        counts.assign(npx, 0u);
+        std::vector<double> err(npx);
+        for (;;) {
+            chk(rt_progressive_error_async(x.c, x.err, nullptr), "rt_progressive_error_async");
+            (void)collect();   // a half-count snapshot above 2.0 is not the image's
+            chk(rt_memcpy_d2h(x.c, err.data(), x.err, npx * sizeof(double)), "rt_memcpy_d2h");
+            chk(rt_progressive_counts(x.c, counts.data()), "rt_progressive_counts");
+            size_t active = 0;
+            for (size_t p = 0; p < npx; ++p)
+                if (err[p] > tolerance && counts[p] < spp) {
+                    counts[p] = (uint32_t)std::min<uint64_t>(2ull * counts[p], spp);
+                    ++active;
+                }
+            if (active == 0) break;
+            chk(rt_progressive_extend_map_async(x.c, counts.data(), nullptr, nullptr, nullptr), "rt_progressive_extend_map_async");
+            const uint64_t before = total.samples;
+            (void)collect();
+            step(active, total.samples - before);
+        }
+        chk(rt_progressive_snapshot_map_async(x.c, nullptr, x.buf, nullptr, nullptr), "rt_progressive_snapshot_map_async");
+        if (collect()) throw Panic("assertion failed: a pixel channel exceeded 2.0 (color.rs:55-57)");
+        chk(rt_memcpy_d2h(x.c, img.data.data(), x.buf, npx * 3), "rt_memcpy_d2h");
+        chk(rt_progressive_end(x.c), "rt_progressive_end");
+        RenderStat stat(std::chrono::steady_clock::now() - t0, npx, total);
+        return {std::move(img), stat};
+    }
+
   private:
     void render_blocks(const rt_scene& rs, const Camera& camera, uint32_t max_bounces, uint32_t spp, RgbImage& img,
                        rt_stats& total, uint32_t B, bool print_blocks) {

@@ -81,13 +81,18 @@ def RT_KERNEL_SPLIT(kernel_id):
     return (kernel_id >> 9) & 1
 
 
+def RT_KERNEL_ITEMS(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_ITEMS: a session's item-table kernel ran (a non-uniform map)."""
+    return (kernel_id >> 10) & 1
+
+
 def kernel_info(kernel_id):
     """rt_stats.kernel_id decoded (include/rt_mi355x.h RT_KERNEL_*): the trace_paths instantiation that ran."""
     if kernel_id == 0:
         return None
     return {"T": "double" if kernel_id & 1 else "float", "W": (kernel_id >> 1) & 7, "root2": bool((kernel_id >> 4) & 1),
             "mode": (kernel_id >> 5) & 3, "camq": bool((kernel_id >> 7) & 1), "mega": bool((kernel_id >> 8) & 1),
-            "split": bool(RT_KERNEL_SPLIT(kernel_id))}
+            "split": bool(RT_KERNEL_SPLIT(kernel_id)), "items": bool(RT_KERNEL_ITEMS(kernel_id))}
 
 
 def kernel_name(kernel_id):
@@ -96,6 +101,8 @@ def kernel_name(kernel_id):
     if k is None:
         return None
     b = lambda v: "true" if v else "false"
+    if k["items"]:   # trace_paths_items<T,W,CAMQ,MEGA> (finish_window_list<T> follows it)
+        return f"trace_paths_items<{k['T']},{k['W']},{b(k['camq'])},{b(k['mega'])}>"
     if k["split"]:   # trace_paths_split<T,W,CAMQ,MEGA> (finish_records<T> follows it)
         return f"trace_paths_split<{k['T']},{k['W']},{b(k['camq'])},{b(k['mega'])}>"
     return f"trace_paths<{k['T']},{k['W']},{b(k['root2'])},{k['mode']},{b(k['camq'])},{b(k['mega'])}>"
@@ -127,6 +134,8 @@ EXPORTED = [
     "rt_context_set_scene", "rt_render_async", "rt_context_collect", "rt_device_alloc", "rt_device_free",
     "rt_memcpy_d2h", "rt_last_error", "rt_version", "rt_render_split_async", "rt_split_plan",
     "rt_progressive_bytes", "rt_progressive_begin", "rt_progressive_extend_async", "rt_progressive_end",
+    "rt_progressive_extend_map_async", "rt_progressive_snapshot_map_async", "rt_progressive_counts",
+    "rt_progressive_error_async", "rt_progressive_map_plan",
 ]
 
 _lib = None
@@ -192,6 +201,11 @@ def load_library(path=None):
     lib.rt_progressive_begin.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), u64]
     lib.rt_progressive_extend_async.argtypes = [vp, u32, vp, vp, vp]
     lib.rt_progressive_end.argtypes = [vp]
+    lib.rt_progressive_extend_map_async.argtypes = [vp, P(u32), vp, vp, vp]
+    lib.rt_progressive_snapshot_map_async.argtypes = [vp, P(u32), vp, vp, vp]
+    lib.rt_progressive_counts.argtypes = [vp, P(u32)]
+    lib.rt_progressive_error_async.argtypes = [vp, vp, vp]
+    lib.rt_progressive_map_plan.argtypes = [u64, P(u32), P(u32), u32, P(u32), P(u64), P(u32), u64]
     lib.rt_context_collect.argtypes = [vp, vp, P(RtStats)]
     lib.rt_device_alloc.argtypes = [vp, ctypes.c_size_t, P(vp)]
     lib.rt_device_free.argtypes = [vp, vp]

@@ -75,33 +75,67 @@ def check_schedule(schedule):
     return counts
 
 
+def check_adaptive(spp_min, spp_max, tolerance):
+    """GpuRenderer.adaptive's arguments checked before any GPU call: 1 <= spp_min <= spp_max, a tolerance that is
+    a number (not NaN).  Returns (spp_min, spp_max, tolerance) as (int, int, float)."""
+    for name, n in (("spp_min", spp_min), ("spp_max", spp_max)):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise ValueError(f"{name} must be an int, not {n!r}")
+    if spp_min < 1:
+        raise ValueError(f"spp_min must be 1 or more, not {spp_min}")
+    if spp_min > spp_max:
+        raise ValueError(f"spp_min ({spp_min}) is above spp_max ({spp_max})")
+    tolerance = float(tolerance)
+    if tolerance != tolerance:
+        raise ValueError("tolerance is NaN")
+    return int(spp_min), int(spp_max), tolerance
+
+
 class ProgressiveSession:
     """One progressive session on a GpuRenderer's context (rt_progressive_*, include/rt_mi355x.h): the
     samples traced so far stay in a record buffer, extend() adds more and takes an image at any count.  The
-    image after n samples is bit for bit render_flat's at spp = n.  A context manager; close() frees the buffer."""
+    image after n samples is bit for bit render_flat's at spp = n.  extend_map() gives every pixel a count of
+    its own (pixel p's value is render_flat's at spp = counts[p]), snapshot() reduces at any earlier counts and
+    error() is the half-buffer estimate adaptive sampling steers by.  Pixels are indexed in the range's compact
+    order, the order of the outputs.  A context manager; close() frees the buffer."""
 
     def __init__(self, renderer, max_bounces, spp_capacity, flat, cam, tile_range=None, max_bytes=0):
         self.renderer, self.lib = renderer, renderer.lib
         self.capacity = int(spp_capacity)
-        self._done = 0
         self._open = False
         if renderer._scene_flat is not flat:
             renderer.set_scene(flat)
         tr = tile_range if tile_range is not None else abi.RtTileRange(0, 1, cam.image_height, 0, cam.image_width)
         self.npx = tr.row_count * tr.col_count
+        self._counts = np.zeros(self.npx, dtype=np.uint32)
         abi.check(self.lib, self.lib.rt_progressive_begin(renderer.ctx, ctypes.byref(cam), max_bounces, spp_capacity,
                                                           renderer.seed, renderer.flags, ctypes.byref(tr), max_bytes))
         self._open = True
         renderer._session = self
 
     @property
-    def done(self):
-        """Samples per pixel traced so far."""
-        return self._done
+    def counts(self):
+        """Samples traced so far per pixel: np.uint32[n] (a copy)."""
+        return self._counts.copy()
 
-    def extend(self, spp_total, want_linear=False, image=True, stream=None):
-        """Trace samples [done, spp_total) and reduce [0, spp_total): (rgb [n,3] u8, linear [n,3] f64 | None,
-        RtStats, rc) like render_flat; rc is RT_OK or RT_ERR_RANGE.  image=False: trace only, returns the RtStats."""
+    @property
+    def done(self):
+        """Samples every pixel holds: the minimum over the pixels (a uniform session: its sample count)."""
+        return int(self._counts.min())
+
+    def _refresh(self):
+        abi.check(self.lib, self.lib.rt_progressive_counts(self.renderer.ctx,
+                                                           self._counts.ctypes.data_as(ctypes.POINTER(abi.u32))))
+
+    def _map_argument(self, counts, what):
+        a = np.ascontiguousarray(counts)
+        if a.shape != (self.npx,) or a.dtype.kind not in "iu" or (a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF)):
+            raise ValueError(f"{what} must be {self.npx} unsigned sample counts, one per pixel of the session's range")
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def _run(self, call, want_linear, image, stream):
+        """call(d_rgb8, d_linear) on fresh device buffers, then collect and read back: (rgb [n,3] u8, linear
+        [n,3] f64 | None, RtStats, rc); image=False: no buffers, returns the RtStats."""
         if not self._open:
             raise RuntimeError("the progressive session is closed")
         lib, ctx = self.lib, self.renderer.ctx
@@ -111,9 +145,8 @@ class ProgressiveSession:
                 abi.check(lib, lib.rt_device_alloc(ctx, self.npx * 3, ctypes.byref(d_rgb)))
                 if want_linear:
                     abi.check(lib, lib.rt_device_alloc(ctx, self.npx * 3 * 8, ctypes.byref(d_lin)))
-            abi.check(lib, lib.rt_progressive_extend_async(ctx, spp_total, d_rgb if image else None,
-                                                           d_lin if image and want_linear else None, stream))
-            self._done = spp_total
+            abi.check(lib, call(d_rgb if image else None, d_lin if image and want_linear else None))
+            self._refresh()
             st = abi.RtStats()
             rc = abi.check(lib, lib.rt_context_collect(ctx, stream, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
             if not image:
@@ -130,6 +163,47 @@ class ProgressiveSession:
             if d_lin:
                 lib.rt_device_free(ctx, d_lin)
         return rgb, lin, st, rc
+
+    def extend(self, spp_total, want_linear=False, image=True, stream=None):
+        """Trace samples [done, spp_total) and reduce [0, spp_total): (rgb [n,3] u8, linear [n,3] f64 | None,
+        RtStats, rc) like render_flat; rc is RT_OK or RT_ERR_RANGE.  image=False: trace only, returns the RtStats."""
+        ctx = self.renderer.ctx
+        return self._run(lambda rgb, lin: self.lib.rt_progressive_extend_async(ctx, spp_total, rgb, lin, stream),
+                         want_linear, image, stream)
+
+    def extend_map(self, targets, want_linear=False, image=True, stream=None):
+        """rt_progressive_extend_map_async: trace samples [counts[p], targets[p]) of every pixel p and reduce pixel
+        p at targets[p].  Returns what extend() returns."""
+        t = self._map_argument(targets, "targets")
+        ctx, tp = self.renderer.ctx, t.ctypes.data_as(ctypes.POINTER(abi.u32))
+        return self._run(lambda rgb, lin: self.lib.rt_progressive_extend_map_async(ctx, tp, rgb, lin, stream),
+                         want_linear, image, stream)
+
+    def snapshot(self, counts=None, want_linear=False, stream=None):
+        """rt_progressive_snapshot_map_async: the image with pixel p at counts[p] <= its samples so far (None: at
+        every pixel's own count), nothing traced.  (rgb, linear | None, RtStats, rc)."""
+        c = None if counts is None else self._map_argument(counts, "counts")
+        ctx, cp = self.renderer.ctx, None if c is None else c.ctypes.data_as(ctypes.POINTER(abi.u32))
+        return self._run(lambda rgb, lin: self.lib.rt_progressive_snapshot_map_async(ctx, cp, rgb, lin, stream),
+                         want_linear, True, stream)
+
+    def error(self, stream=None, stats=False):
+        """rt_progressive_error_async: np.float64[n], per pixel the largest channel difference between its linear
+        value at counts[p] and at counts[p] // 2 samples; inf below 2 samples.  stats=True: (error, RtStats)."""
+        if not self._open:
+            raise RuntimeError("the progressive session is closed")
+        lib, ctx = self.lib, self.renderer.ctx
+        d_err = ctypes.c_void_p()
+        abi.check(lib, lib.rt_device_alloc(ctx, self.npx * 8, ctypes.byref(d_err)))
+        try:
+            abi.check(lib, lib.rt_progressive_error_async(ctx, d_err, stream))
+            st = abi.RtStats()
+            abi.check(lib, lib.rt_context_collect(ctx, stream, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
+            err = np.empty(self.npx, dtype=np.float64)
+            abi.check(lib, lib.rt_memcpy_d2h(ctx, err.ctypes.data, d_err, self.npx * 8))
+        finally:
+            lib.rt_device_free(ctx, d_err)
+        return (err, st) if stats else err
 
     def close(self):
         if self._open:
@@ -280,3 +354,37 @@ class GpuRenderer(Renderer):
                 img = rgb.reshape(cam.image_height, cam.image_width, 3)
                 yield n, img, RenderStat(dt, cam.image_width * cam.image_height, st.kernel_ms, st.samples,
                                          st.ray_segments, range_error=rc == abi.RT_ERR_RANGE)
+
+    def adaptive(self, max_bounces, spp_min, spp_max, tolerance, scene, camera):
+        """Adaptive sampling: every pixel gets spp_min samples, then the pixels whose error estimate
+        (ProgressiveSession.error) is above `tolerance` double their count, up to spp_max, until none is left.
+        Returns (image HxWx3 uint8, counts HxW uint32, RenderStat); pixel p of the image equals render()'s at
+        spp = counts[p], and stat.samples is the total traced (counts.sum()).  The live path only."""
+        spp_min, spp_max, tolerance = check_adaptive(spp_min, spp_max, tolerance)   # before any GPU call
+        t0 = time.perf_counter()
+        cam = camera.abi if hasattr(camera, "abi") else camera
+        ms, samples, segs = 0.0, 0, 0
+
+        def add(st):
+            nonlocal ms, samples, segs
+            ms, samples, segs = ms + st.kernel_ms, samples + st.samples, segs + st.ray_segments
+
+        with self.begin_progressive(max_bounces, spp_max, scene, cam) as session:
+            add(session.extend(spp_min, image=False))
+            while True:
+                err, st = session.error(stats=True)
+                add(st)
+                counts = session.counts
+                active = (err > tolerance) & (counts < spp_max)
+                if not active.any():
+                    break
+                counts[active] = np.minimum(2 * counts[active].astype(np.uint64), spp_max).astype(np.uint32)
+                add(session.extend_map(counts, image=False))
+            rgb, _, st, rc = session.snapshot()
+            add(st)
+            counts = session.counts
+        dt = time.perf_counter() - t0
+        if rc == abi.RT_ERR_RANGE:
+            raise abi.RtError(rc, "a pixel channel exceeded 2.0 (reference: Color::to_u8_array panics)")
+        h, w = cam.image_height, cam.image_width
+        return rgb.reshape(h, w, 3), counts.reshape(h, w), RenderStat(dt, w * h, ms, samples, segs)
