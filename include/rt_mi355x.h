@@ -316,6 +316,53 @@ int rt_progressive_error_async(rt_context* ctx, void* d_error, void* stream);
 int rt_progressive_map_plan(uint64_t n_pixels, const uint32_t* done, const uint32_t* target, uint32_t resident_waves,
                             uint32_t* samples_per_item, uint64_t* n_items, uint32_t* items, uint64_t items_capacity);
 
+/* ---- refinement planned on the device: the doubling policy without per-pixel host work ----
+ * One step of the policy "double the pixels whose estimate is above the tolerance": with err_p the estimate of
+ * rt_progressive_error_async, active = (err_p > tolerance) and (done_p < spp_max), and the active pixels go to
+ * min(2 done_p, spp_max).  A run is the calls from the first one until it returns *n_active == 0; a session
+ * carries one run.  The counts, the linear values the estimate compares, the selection, the lists and the item
+ * table stay on the device; no step uploads a per-pixel or per-item table.  The counts and the image of a run are
+ * exactly those of the same policy driven from the host with rt_progressive_error_async and
+ * rt_progressive_extend_map_async.
+ *   First call: the session must be uniform at n0 >= 1 samples.  The whole frame is reduced at n0 and, if
+ *     n0 >= 2, at n0 / 2, into buffers the session owns (2 x 24 bytes per pixel; the lists and counts take
+ *     another 17).
+ *   Later calls: the candidates are the pixels the previous call traced, all at one count n_k.  At n_k == spp_max
+ *     they are finished (*n_active = 0, nothing runs).  Otherwise they alone are reduced once, at n_k; their value
+ *     at n_k / 2 is the one kept from the step before.
+ * The selection runs in kernels (estimate and flag, block counts, a scan of the block counts, a scatter, each a
+ * launch of its own), then the call copies ONE 16-byte record down through the session's pinned buffer and waits
+ * for it: the number of active pixels.  That wait is the only host synchronisation of a step, and the reason
+ * the call has no _async suffix.  From that number the host plans as rt_progressive_map_plan does (its mean is
+ * exact here), a kernel expands the active list into the item table, and the item-table kernel traces
+ * [n_k, min(2 n_k, spp_max)) of the active pixels asynchronously on `stream`, under the cross-stream rule of
+ * rt_render_async.  *n_active: the pixels selected; *n_samples: the samples enqueued; *n_active == 0: converged,
+ * nothing traced.  A NaN estimate is not active.
+ * rt_context_collect after it: samples and ray_segments count what was traced (over a run they sum to the counts'
+ * total above n0), pixels gets the pixel count once per call that enqueued work, RT_KERNEL_SPLIT and
+ * RT_KERNEL_ITEMS are set by a step that traced.  bounce_iters gets a pixel's K once per reduction of that pixel:
+ * far fewer than on the host-driven path, which reduces every pixel twice per estimate.  kernel_ms spans the
+ * readback's wait.
+ * With the other calls: during a run the device counts are the session's; rt_progressive_counts and every map,
+ * extend or error call first copy them down (4 bytes per pixel), then do what they always do.
+ * rt_progressive_snapshot_map_async(ctx, NULL, ...) during or after a run reduces each class the run built from
+ * its device list (one launch per count, no host pass, no upload), with the outputs and the return code of the
+ * host path.  A call that traces into the session (an extend or a map with new samples) ends the run's claim on
+ * the counts: a later rt_progressive_refine is RT_ERR_UNSUPPORTED.
+ * RT_ERR_INVALID: no session open, a NULL output, a NaN tolerance, spp_max above spp_capacity or below the current
+ * count, a session without samples, tolerance or spp_max differing from the run's first call;
+ * RT_ERR_UNSUPPORTED: a run started on a non-uniform session, a call after another call has traced into the
+ * session (see above), more than 0x7FFFFFFF work items in a step.  Out of scope: any policy but doubling and any
+ * non-uniform start; rt_progressive_extend_map_async takes every map. */
+int rt_progressive_refine(rt_context* ctx, double tolerance, uint32_t spp_max, void* stream, uint64_t* n_active,
+                          uint64_t* n_samples);
+/* Diagnostic: the item table the last rt_progressive_refine step built on the device ({pixel, first, end, 0}
+ * records), copied to the host; items, items_capacity and n_items as in rt_progressive_map_plan.  A step that
+ * selected nothing (or no step yet) has no items and samples_per_item 0.  Synchronises the session's stream.
+ * RT_ERR_INVALID: no session open, a NULL output, items given with items_capacity below *n_items (which is set). */
+int rt_progressive_refine_items(rt_context* ctx, uint32_t* samples_per_item, uint64_t* n_items, uint32_t* items,
+                                uint64_t items_capacity);
+
 /* Close the session: synchronises the stream of its last extend and frees the record buffer.
  * RT_ERR_INVALID: no session open.  rt_context_destroy ends an open session. */
 int rt_progressive_end(rt_context* ctx);

@@ -177,6 +177,11 @@ template <typename T> static int upload_scene(DeviceScene<T>& d, const SceneTabl
     return rc;
 }
 
+// The pixels of one reduction that share a sample count: list[first .. first + n) of the reduction's index list.
+struct CountClass {
+    uint32_t spp, first, n;
+};
+
 struct rt_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -218,6 +223,21 @@ struct rt_context {
         PinnedStage stage;
         DeviceBuffer tables, lin_full, lin_half;
         void set_done(uint32_t n) { std::fill(done.begin(), done.end(), n); done_min = done_max = n; }
+        // The refinement run (rt_progressive_refine; one per session): its tolerance and cap, the candidates of the
+        // next step (the n_cand pixels of act[cur], all at n_k samples; the run's first step takes every pixel),
+        // the classes of the pixels that stopped (spp, first, n: their pixels are cls_list[first .. first + n) on
+        // the device), and the last step's plan.  While a run is unbroken the device array counts is what the
+        // pixels hold, and done_stale says that `done` has not been copied down since the last step.
+        struct Refine {
+            bool started = false, broken = false;
+            double tol = 0.0;
+            uint32_t spp_max = 0, n_k = 0, n_cand = 0, cls_used = 0, S = 0;
+            int cur = 0;
+            uint64_t n_items = 0;
+            std::vector<CountClass> cls;
+        } run;
+        bool done_stale = false;
+        DeviceBuffer counts, act[2], cls_list, sel, blk, ret, items, lin_cur, lin_new;
     } prog;
 };
 
@@ -733,10 +753,6 @@ static int launch_window(rt_context* c, const FrameArgs& a, const SessionWindow&
 }
 
 // ---- per-pixel counts (rt_progressive_extend_map_async and its kin; DESIGN.md §4 "Per-pixel counts") ----
-// The pixels of one reduction that share a sample count: list[first .. first + n) of the reduction's index list.
-struct CountClass {
-    uint32_t spp, first, n;
-};
 static_assert(sizeof(MapItem) == kMapItemWords * sizeof(uint32_t), "the plan's records are the kernel's");
 constexpr size_t kMaxCountClasses = 256;   // distinct counts one reduction may have (a launch each)
 
@@ -1048,6 +1064,7 @@ static int extend_uniform(rt_context* c, const std::string& who, uint32_t spp_to
     rc = f32 ? launch_window<float>(c, a, w, st) : launch_window<double>(c, a, w, st);
     if (rc != RT_OK) return rc;
     if ((rc = end_launch(c, st, n_pix, n_pix * (uint64_t)(spp_total - done))) != RT_OK) return rc;
+    if (w.trace) s.run.broken = s.run.started;   // a refinement run's lists no longer say what the pixels hold
     s.set_done(spp_total);
     s.stream = st;
     s.have_stream = true;
@@ -1124,6 +1141,7 @@ static int run_map(rt_context* c, const std::string& who, const uint32_t* target
         set_id = false;
     }
     if (target) {
+        if (n_items) s.run.broken = s.run.started;   // as in extend_uniform
         s.done.assign(target, target + n_pix);
         s.done_min = *std::min_element(s.done.begin(), s.done.end());
         s.done_max = *std::max_element(s.done.begin(), s.done.end());
@@ -1140,10 +1158,204 @@ static int open_session(rt_context* c, const std::string& who) {
     return RT_OK;
 }
 
+// After a step of rt_progressive_refine the counts are on the device: copy them down (4 bytes per pixel) before
+// a call reads `done`.
+static int sync_done(rt_context* c) {
+    rt_context::Session& s = c->prog;
+    if (!s.done_stale) return RT_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (s.have_stream) HIPCHK(hipStreamSynchronize(s.stream));
+    HIPCHK(hipMemcpy(s.done.data(), s.counts.p, s.done.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    s.done_min = *std::min_element(s.done.begin(), s.done.end());
+    s.done_max = *std::max_element(s.done.begin(), s.done.end());
+    s.done_stale = false;
+    return RT_OK;
+}
+
+// ---- refinement on the device (rt_progressive_refine; DESIGN.md §4 "Planning on the device") ----
+// finish_window over every pixel of the session at `spp` samples into lin (no tracing).
+template <typename T>
+static int reduce_uniform(rt_context* c, const rt_context::Session& s, uint32_t spp, void* lin, hipStream_t st) {
+    const SessionWindow w{(char*)s.rec, s.cap, spp, spp, 1u, 1u, false, true};
+    return launch_window<T>(c, session_frame(s, spp, nullptr, lin), w, st);
+}
+
+// rt_progressive_snapshot_map_async(ctx, NULL, ...) of a session in an unbroken run: one finish_window_list per
+// class the run has built, then one over the candidates of its next step, which all hold n_k samples.
+static int snapshot_run(rt_context* c, void* d_rgb8, void* d_linear, hipStream_t st) {
+    rt_context::Session& s = c->prog;
+    const rt_context::Session::Refine& r = s.run;
+    const bool f32 = (s.flags & RT_FLAG_F32) != 0;
+    int rc = begin_launch(c, st);
+    if (rc != RT_OK) return rc;
+    if (!r.cls.empty()) {
+        const uint32_t* list = (const uint32_t*)s.cls_list.p;
+        rc = f32 ? launch_classes<float>(c, s, r.cls, list, d_rgb8, d_linear, true, st)
+                 : launch_classes<double>(c, s, r.cls, list, d_rgb8, d_linear, true, st);
+        if (rc != RT_OK) return rc;
+    }
+    if (r.n_cand) {
+        const std::vector<CountClass> last{CountClass{r.n_k, 0u, r.n_cand}};
+        const uint32_t* list = (const uint32_t*)s.act[r.cur].p;
+        rc = f32 ? launch_classes<float>(c, s, last, list, d_rgb8, d_linear, r.cls.empty(), st)
+                 : launch_classes<double>(c, s, last, list, d_rgb8, d_linear, r.cls.empty(), st);
+        if (rc != RT_OK) return rc;
+    }
+    s.stream = st;
+    s.have_stream = true;
+    return end_launch(c, st, (uint64_t)s.rg.row_count * s.rg.col_count, 0u);
+}
+
+extern "C" int rt_progressive_refine(rt_context* c, double tolerance, uint32_t spp_max, void* stream,
+                                     uint64_t* n_active, uint64_t* n_samples) {
+    const std::string who = "rt_progressive_refine";
+    if (!c || !n_active || !n_samples) return fail(RT_ERR_INVALID, who + ": NULL argument");
+    *n_active = 0;
+    *n_samples = 0;
+    if (!c->prog.open) return fail(RT_ERR_INVALID, who + ": no session open on this context");
+    if (tolerance != tolerance) return fail(RT_ERR_INVALID, who + ": tolerance is NaN");
+    rt_context::Session& s = c->prog;
+    rt_context::Session::Refine& r = s.run;
+    if (r.started) {
+        if (tolerance != r.tol || spp_max != r.spp_max)
+            return fail(RT_ERR_INVALID, who + ": tolerance or spp_max differs from the run's first call");
+        if (r.broken)
+            return fail(RT_ERR_UNSUPPORTED, who + ": another call has traced into the session since the run's last "
+                                                  "step (rt_progressive_extend_map_async takes any map)");
+    } else {
+        if (spp_max > s.cap) return fail(RT_ERR_INVALID, who + ": spp_max above the session's spp_capacity");
+        if (spp_max < s.done_max) return fail(RT_ERR_INVALID, who + ": spp_max below the samples a pixel already holds");
+        if (s.done_min != s.done_max)
+            return fail(RT_ERR_UNSUPPORTED, who + ": a run starts on a uniform session (rt_progressive_extend_map_async "
+                                                  "takes any map)");
+        if (s.done_min == 0u) return fail(RT_ERR_INVALID, who + ": the session holds no sample yet");
+    }
+    const bool first = !r.started, f32 = (s.flags & RT_FLAG_F32) != 0;
+    const uint32_t n_pix = s.rg.row_count * s.rg.col_count;
+    const uint32_t n_k = first ? s.done_min : r.n_k, n_cand = first ? n_pix : r.n_cand;
+    if (!first && (n_cand == 0u || n_k >= spp_max)) {   // converged, or every candidate is at the cap
+        r.S = 0u;
+        r.n_items = 0u;   // this step built no table
+        return RT_OK;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = RT_OK;
+    if (first) {
+        const size_t words = (size_t)n_pix * sizeof(uint32_t), lin_bytes = (size_t)n_pix * 3u * sizeof(double);
+        const size_t blocks = ((size_t)n_pix + kRefineBlock - 1u) / kRefineBlock;
+        for (DeviceBuffer* b : {&s.counts, &s.act[0], &s.act[1], &s.cls_list})
+            if ((rc = reserve(*b, words)) != RT_OK) return rc;
+        if ((rc = reserve(s.sel, n_pix)) != RT_OK) return rc;
+        if ((rc = reserve(s.blk, blocks * sizeof(uint32_t))) != RT_OK) return rc;
+        if ((rc = reserve(s.ret, 4u * sizeof(uint32_t))) != RT_OK) return rc;
+        if ((rc = reserve(s.lin_cur, lin_bytes)) != RT_OK) return rc;
+        if ((rc = reserve(s.lin_new, lin_bytes)) != RT_OK) return rc;
+    }
+    if ((rc = stage_reserve(s.stage, 4u * sizeof(uint32_t))) != RT_OK) return rc;
+    if ((rc = begin_launch(c, st)) != RT_OK) return rc;   // the session shares the counter, scratch and camera tables
+    // the estimate's reductions: the whole frame at n0 / 2 and n0 at first, later the candidates alone at n_k,
+    // whose values at n_k / 2 (the count they held a step ago) are still in lin_cur
+    const uint32_t* const list = first ? nullptr : (const uint32_t*)s.act[r.cur].p;
+    if (first) {
+        if (n_k >= 2u) {
+            rc = f32 ? reduce_uniform<float>(c, s, n_k / 2u, s.lin_cur.p, st) : reduce_uniform<double>(c, s, n_k / 2u, s.lin_cur.p, st);
+            if (rc != RT_OK) return rc;
+        }
+        rc = f32 ? reduce_uniform<float>(c, s, n_k, s.lin_new.p, st) : reduce_uniform<double>(c, s, n_k, s.lin_new.p, st);
+    } else {
+        const std::vector<CountClass> cand{CountClass{n_k, 0u, n_cand}};
+        rc = f32 ? launch_classes<float>(c, s, cand, list, nullptr, s.lin_new.p, true, st)
+                 : launch_classes<double>(c, s, cand, list, nullptr, s.lin_new.p, true, st);
+    }
+    if (rc != RT_OK) return rc;
+    // select, scan, scatter: the next active list into the other act buffer, the rest behind the earlier classes
+    const uint32_t nb = (n_cand + kRefineBlock - 1u) / kRefineBlock;
+    const int nxt = first ? 0 : 1 - r.cur;
+    uint32_t* const d_blk = (uint32_t*)s.blk.p;
+    hipLaunchKernelGGL(refine_select, dim3(nb), dim3(kRefineBlock), 0, st, list, n_cand, n_k, tolerance,
+                       n_k < spp_max ? 1u : 0u, (double*)s.lin_cur.p, (const double*)s.lin_new.p, (uint32_t*)s.counts.p,
+                       (uint8_t*)s.sel.p, d_blk);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(refine_scan, dim3(1), dim3(kRefineBlock), 0, st, d_blk, nb, (uint32_t*)s.ret.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(refine_scatter, dim3(nb), dim3(kRefineBlock), 0, st, list, n_cand, (const uint8_t*)s.sel.p,
+                       (const uint32_t*)d_blk, (uint32_t*)s.act[nxt].p, (uint32_t*)s.cls_list.p + r.cls_used);
+    HIPCHK(hipGetLastError());
+    // the step's one readback, and its one wait: how many pixels go on
+    HIPCHK(hipMemcpyAsync(s.stage.p, s.ret.p, 4u * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint32_t A = *(const volatile uint32_t*)s.stage.p;
+    if (A > n_cand) return fail(RT_ERR_HIP, who + ": internal: more active pixels than candidates");
+    if (n_cand - A) r.cls.push_back(CountClass{n_k, r.cls_used, n_cand - A});
+    r.cls_used += n_cand - A;
+    r.started = true;
+    r.tol = tolerance;
+    r.spp_max = spp_max;
+    r.cur = nxt;
+    r.n_cand = A;
+    r.n_k = n_k;
+    r.S = 0u;
+    r.n_items = 0u;
+    s.done_stale = true;
+    s.stream = st;
+    s.have_stream = true;
+    if (A == 0u) return end_launch(c, st, n_pix, 0u);
+    // the plan: rt_progressive_map_plan's for A pixels that all go from n_k to t (its mean is exact)
+    const uint32_t t = (uint32_t)std::min<uint64_t>(2ull * n_k, spp_max);
+    const uint32_t waves = (uint32_t)c->n_cu * 4u * (uint32_t)(f32 ? kWavesSplit<float> : kWavesSplit<double>);
+    uint32_t S = 0;
+    uint64_t planned = 0;
+    const int prc = split_plan(A, t - n_k, waves, &S, &planned);
+    const bool grid = prc == kPlanOk && S % kSplitGrain == 0u;
+    const uint32_t base = grid ? n_k - n_k % kSplitGrain : n_k;
+    const uint32_t nsub = grid ? split_nsub(t - base, S) : 1u;
+    const uint64_t n_items = (uint64_t)A * nsub;
+    if (prc != kPlanOk || n_items > kSplitMaxItems) {
+        r.broken = true;   // the active pixels stay at n_k, as the device counts say
+        return fail(prc != kPlanOk ? prc : RT_ERR_UNSUPPORTED, who + ": no plan for this step (more than 0x7FFFFFFF work items)");
+    }
+    if ((rc = ensure_bytes(s.items, (size_t)n_items * sizeof(MapItem), st)) != RT_OK) return rc;
+    hipLaunchKernelGGL(refine_expand, dim3((A + kRefineBlock - 1u) / kRefineBlock), dim3(kRefineBlock), 0, st,
+                       (const uint32_t*)s.act[nxt].p, A, (uint32_t*)s.counts.p, n_k, t, base, grid ? S : t - n_k, nsub,
+                       (MapItem*)s.items.p);
+    HIPCHK(hipGetLastError());
+    const uint64_t traced = (uint64_t)A * (t - n_k);
+    const uint32_t item_spp = (uint32_t)std::max<uint64_t>(1u, traced / n_items);   // the mean item, as run_map
+    rc = f32 ? launch_items<float>(c, s, (const MapItem*)s.items.p, (uint32_t)n_items, item_spp, st)
+             : launch_items<double>(c, s, (const MapItem*)s.items.p, (uint32_t)n_items, item_spp, st);
+    if (rc != RT_OK) return rc;
+    r.n_k = t;
+    r.S = S;
+    r.n_items = n_items;
+    *n_active = A;
+    *n_samples = traced;
+    return end_launch(c, st, n_pix, traced);
+}
+
+extern "C" int rt_progressive_refine_items(rt_context* c, uint32_t* samples_per_item, uint64_t* n_items, uint32_t* items,
+                                           uint64_t items_capacity) {
+    const std::string who = "rt_progressive_refine_items";
+    if (!c || !samples_per_item || !n_items) return fail(RT_ERR_INVALID, who + ": NULL argument");
+    *samples_per_item = 0;
+    *n_items = 0;
+    if (!c->prog.open) return fail(RT_ERR_INVALID, who + ": no session open on this context");
+    rt_context::Session& s = c->prog;
+    *samples_per_item = s.run.n_items ? s.run.S : 0u;
+    *n_items = s.run.n_items;
+    if (!items || s.run.n_items == 0u) return RT_OK;
+    if (items_capacity < s.run.n_items) return fail(RT_ERR_INVALID, who + ": items_capacity below the item count");
+    HIPCHK(hipSetDevice(c->device));
+    if (s.have_stream) HIPCHK(hipStreamSynchronize(s.stream));
+    HIPCHK(hipMemcpy(items, s.items.p, (size_t)s.run.n_items * sizeof(MapItem), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 extern "C" int rt_progressive_extend_async(rt_context* c, uint32_t spp_total, void* d_rgb8, void* d_linear, void* stream) {
     const std::string who = "rt_progressive_extend_async";
     int rc = open_session(c, who);
     if (rc != RT_OK) return rc;
+    if ((rc = sync_done(c)) != RT_OK) return rc;
     rt_context::Session& s = c->prog;
     if (s.done_min == s.done_max) return extend_uniform(c, who, spp_total, d_rgb8, d_linear, stream);
     // after a non-uniform map: every pixel goes from its own count to spp_total
@@ -1163,6 +1375,7 @@ extern "C" int rt_progressive_extend_map_async(rt_context* c, const uint32_t* sp
     if (rc != RT_OK) return rc;
     rt_context::Session& s = c->prog;
     if (!spp_target) return fail(RT_ERR_INVALID, who + ": spp_target is NULL");
+    if ((rc = sync_done(c)) != RT_OK) return rc;
     const bool out = d_rgb8 != nullptr || d_linear != nullptr;
     bool same = s.done_min == s.done_max;
     for (size_t p = 0; p < s.done.size(); ++p) {
@@ -1186,6 +1399,9 @@ extern "C" int rt_progressive_snapshot_map_async(rt_context* c, const uint32_t* 
     if (rc != RT_OK) return rc;
     rt_context::Session& s = c->prog;
     if (!d_rgb8 && !d_linear) return fail(RT_ERR_INVALID, who + ": both outputs are NULL");
+    // every pixel at its own count, during or after a refinement run: the classes are already on the device
+    if (!spp_count && s.run.started && !s.run.broken) return snapshot_run(c, d_rgb8, d_linear, (hipStream_t)stream);
+    if ((rc = sync_done(c)) != RT_OK) return rc;
     const uint32_t* counts = spp_count ? spp_count : s.done.data();
     for (size_t p = 0; p < s.done.size(); ++p)
         if (counts[p] == 0u || counts[p] > s.done[p])
@@ -1197,9 +1413,10 @@ extern "C" int rt_progressive_snapshot_map_async(rt_context* c, const uint32_t* 
 
 extern "C" int rt_progressive_counts(rt_context* c, uint32_t* out) {
     const std::string who = "rt_progressive_counts";
-    const int rc = open_session(c, who);
+    int rc = open_session(c, who);
     if (rc != RT_OK) return rc;
     if (!out) return fail(RT_ERR_INVALID, who + ": out is NULL");
+    if ((rc = sync_done(c)) != RT_OK) return rc;
     std::copy(c->prog.done.begin(), c->prog.done.end(), out);
     return RT_OK;
 }
@@ -1210,6 +1427,7 @@ extern "C" int rt_progressive_error_async(rt_context* c, void* d_error, void* st
     if (rc != RT_OK) return rc;
     rt_context::Session& s = c->prog;
     if (!d_error) return fail(RT_ERR_INVALID, who + ": d_error is NULL");
+    if ((rc = sync_done(c)) != RT_OK) return rc;
     const uint32_t n_pix = (uint32_t)s.done.size();
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));

@@ -217,4 +217,104 @@ __global__ __launch_bounds__(256) void progressive_error(const double* full, con
     out[i] = e;
 }
 
+// ---- rt_progressive_refine: the selection of one refinement step, on the device ----
+// The candidates of a step are the n pixels list[0 .. n) (list NULL: pixel i itself), in ascending pixel order,
+// all at `count` samples.  Their linear values at `count` are in `fresh`, the values at count / 2 in `cur`.  Four
+// launches, each reading only what an earlier launch wrote (the kernel boundary is the hand-off, as between the
+// trace and finish kernels): refine_select (estimate, flag, count of active per block of kRefineBlock
+// candidates), refine_scan (one workgroup: exclusive scan of the block counts), refine_scatter (stable
+// compaction into the next active list and the list of the pixels that stop at `count`), refine_expand (the
+// active list into the item table trace_paths_items reads).
+constexpr uint32_t kRefineBlock = 256;
+
+// Exclusive prefix of one value per thread over a 256-thread workgroup; *total: the workgroup's sum.
+__device__ inline uint32_t refine_block_scan(uint32_t v, uint32_t* buf, uint32_t* total) {
+    const uint32_t t = threadIdx.x;
+    buf[t] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < kRefineBlock; d <<= 1) {
+        const uint32_t a = t >= d ? buf[t - d] : 0u;
+        __syncthreads();
+        buf[t] += a;
+        __syncthreads();
+    }
+    const uint32_t incl = buf[t];
+    *total = buf[kRefineBlock - 1];
+    __syncthreads();   // the buffer may be written again
+    return incl - v;
+}
+
+// Candidate i: progressive_error's estimate (+inf below 2 samples), fresh moved into cur, counts[p] = count,
+// flags[i] = the estimate is above tol (a NaN is not) and the pixel may still grow; blk[block] = the block's
+// active candidates.
+__global__ __launch_bounds__(256) void refine_select(const uint32_t* list, uint32_t n, uint32_t count, double tol,
+                                                     uint32_t may_grow, double* cur, const double* fresh,
+                                                     uint32_t* counts, uint8_t* flags, uint32_t* blk) {
+    __shared__ uint32_t s_buf[kRefineBlock];
+    const uint32_t i = blockIdx.x * kRefineBlock + threadIdx.x;
+    uint32_t act = 0u;
+    if (i < n) {
+        const size_t p = list ? list[i] : i;
+        double e = __builtin_huge_val();
+        if (count >= 2u) {
+            e = 0.0;
+            for (uint32_t ch = 0; ch < 3u; ++ch) e = fmax(e, fabs(fresh[3u * p + ch] - cur[3u * p + ch]));
+        }
+        for (uint32_t ch = 0; ch < 3u; ++ch) cur[3u * p + ch] = fresh[3u * p + ch];
+        act = (e > tol && may_grow != 0u) ? 1u : 0u;
+        counts[p] = count;
+        flags[i] = (uint8_t)act;
+    }
+    uint32_t total = 0u;
+    (void)refine_block_scan(act, s_buf, &total);
+    if (threadIdx.x == 0u) blk[blockIdx.x] = total;
+}
+
+// blk[0 .. nb): the block counts, replaced by their exclusive prefix sums; ret[0] = their sum (ret: 4 words).
+__global__ __launch_bounds__(256) void refine_scan(uint32_t* blk, uint32_t nb, uint32_t* ret) {
+    __shared__ uint32_t s_buf[kRefineBlock];
+    uint32_t carry = 0u;   // the same in every thread
+    for (uint32_t base = 0; base < nb; base += kRefineBlock) {
+        const uint32_t idx = base + threadIdx.x;
+        const uint32_t v = idx < nb ? blk[idx] : 0u;
+        uint32_t total = 0u;
+        const uint32_t ex = refine_block_scan(v, s_buf, &total);
+        if (idx < nb) blk[idx] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x < 4u) ret[threadIdx.x] = threadIdx.x == 0u ? carry : 0u;
+}
+
+// Stable compaction: the active candidates to next[0 .. A), the others to retired[0 .. n - A), both in candidate
+// (ascending pixel) order.  off: refine_scan's prefix sums.
+__global__ __launch_bounds__(256) void refine_scatter(const uint32_t* list, uint32_t n, const uint8_t* flags,
+                                                      const uint32_t* off, uint32_t* next, uint32_t* retired) {
+    __shared__ uint32_t s_buf[kRefineBlock];
+    const uint32_t first = blockIdx.x * kRefineBlock, i = first + threadIdx.x;
+    const uint32_t act = i < n ? (uint32_t)flags[i] : 0u;
+    uint32_t total = 0u;
+    const uint32_t rank = refine_block_scan(act, s_buf, &total);
+    if (i >= n) return;
+    const uint32_t p = list ? list[i] : i;
+    const uint32_t a0 = off[blockIdx.x];           // active candidates before this block: a0 <= first
+    if (act) next[a0 + rank] = p;                  // < A <= n
+    else retired[(first - a0) + (threadIdx.x - rank)] = p;   // < n - A
+}
+
+// The item table of the step: active pixel i gets nsub records {pixel, first, end, 0}, the samples
+// [max(done, base + j S), min(target, base + (j + 1) S)) (prog_item, rt_progressive_plan.hpp), and its count
+// becomes target.
+__global__ __launch_bounds__(256) void refine_expand(const uint32_t* act, uint32_t n_act, uint32_t* counts,
+                                                     uint32_t done, uint32_t target, uint32_t base, uint32_t S,
+                                                     uint32_t nsub, MapItem* items) {
+    const uint32_t i = blockIdx.x * kRefineBlock + threadIdx.x;
+    if (i >= n_act) return;
+    const uint32_t p = act[i];
+    counts[p] = target;
+    for (uint32_t j = 0; j < nsub; ++j) {
+        const uint32_t a = base + j * S, b = a + S;
+        items[(size_t)i * nsub + j] = MapItem{p, a > done ? a : done, b < target ? b : target, 0u};
+    }
+}
+
 }  // namespace rt

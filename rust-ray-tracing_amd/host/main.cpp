@@ -3,7 +3,7 @@
 //   rt-render [--scene scene.toml] [--width 3840] [--height 2160] [--spp 100] [--bounces 50]
 //             [--seed 0x5EED0001] [--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar]
 //             [--out output.png|.ppm] [--block-size B] [--sample-parallel] [--progressive n1,n2,...]
-//             [--adaptive TOL --spp-min N [--count-map counts.png|.ppm]] [--dump-scene]
+//             [--adaptive TOL --spp-min N [--count-map counts.png|.ppm] [--device-plan]] [--dump-scene]
 //
 // --mode picks which of the reference's renderers is reproduced (include/rt_mi355x.h): the live
 // render_vectorized2 (default), render_vectorized, or the scalar render.
@@ -18,6 +18,8 @@
 // pixel at its count and at half its count) is above TOL double their count, up to --spp, until none is left.
 // It prints per step the active pixels and the samples traced, and at the end the total and its share of
 // pixels x spp.  --count-map PATH writes each pixel's count as grey RGB8, 255 * count / spp.  The live path only.
+// --device-plan (with --adaptive) keeps the estimate, the selection and the item table on the GPU
+// (rt_progressive_refine): the same lines, the same files, a few words between host and device per step.
 //
 // Defaults are main.rs's hard-coded values (scene.toml in the working directory, 3840x2160, 50
 // bounces, 100 spp, camera from (16,2,18.5) looking at the origin, vfov 30, focal 10, no defocus,
@@ -83,7 +85,7 @@ int main(int argc, char** argv) {
     uint64_t seed = 0x5EED0001ull;
     bool dump = false, sample_parallel = false;
     std::string progressive_arg, count_map;
-    bool progressive = false, adaptive = false;
+    bool progressive = false, adaptive = false, device_plan = false;
     double tolerance = 0.0;
     uint32_t spp_min = 0;
     for (int i = 1; i < argc; ++i) {
@@ -115,12 +117,13 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive") { tolerance = std::stod(next()); adaptive = true; }
         else if (a == "--spp-min") spp_min = (uint32_t)std::stoul(next());
         else if (a == "--count-map") count_map = next();
+        else if (a == "--device-plan") device_plan = true;
         else if (a == "--dump-scene") dump = true;
         else if (a == "-h" || a == "--help") {
             std::puts("rt-render [--scene scene.toml] [--width W] [--height H] [--spp S] [--bounces B] [--seed N] "
                       "[--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar] [--out output.png] [--block-size B] "
-                      "[--sample-parallel] [--progressive n1,n2,...] [--adaptive TOL --spp-min N [--count-map PATH]] "
-                      "[--dump-scene]");
+                      "[--sample-parallel] [--progressive n1,n2,...] [--adaptive TOL --spp-min N [--count-map PATH] "
+                      "[--device-plan]] [--dump-scene]");
             return 0;
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -163,8 +166,8 @@ int main(int argc, char** argv) {
         if (tolerance != tolerance) return bad("the tolerance is NaN");
         if (spp_min < 1 || spp_min > spp)
             return bad("--spp-min must be between 1 and --spp (" + std::to_string(spp) + "), the most a pixel gets");
-    } else if (spp_min != 0 || !count_map.empty()) {
-        std::fprintf(stderr, "--spp-min and --count-map go with --adaptive\n");
+    } else if (spp_min != 0 || !count_map.empty() || device_plan) {
+        std::fprintf(stderr, "--spp-min, --count-map and --device-plan go with --adaptive\n");
         return 2;
     }
     try {
@@ -213,7 +216,7 @@ int main(int argc, char** argv) {
             std::fflush(stdout);
         };
         auto [image, stat] = adaptive ? renderer.render_adaptive(bounces, spp_min, spp, tolerance, scene, camera,
-                                                                 pixel_counts, adaptive_step)
+                                                                 pixel_counts, adaptive_step, device_plan)
                              : progressive ? renderer.render_progressive(bounces, spp, scene, camera, counts, step)
                                            : renderer.render(bounces, spp, scene, camera);     // main.rs:64
         save_image(out, image.width, image.height, image.data.data());                         // main.rs:66

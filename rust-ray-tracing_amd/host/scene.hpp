@@ -371,10 +371,13 @@ struct GpuRenderer : Renderer {
     // estimate (rt_progressive_error_async) is above `tolerance` and its count below spp, those pixels double
     // their count (up to spp).  Pixel p of the image is render()'s at counts[p] samples.  step(active pixels,
     // samples the step traced) is called after every refinement step.  The live path only.
+    // device_plan: the steps are rt_progressive_refine's, which estimates, selects and plans on the device; the
+    // counts come down once, at the end.  Same steps, same counts, same image.
     template <typename Step>
     std::pair<RgbImage, RenderStat> render_adaptive(size_t max_bounces, size_t spp_min, size_t spp, double tolerance,
                                                     const Scene& scene, const Camera& camera,
-                                                    std::vector<uint32_t>& counts, Step&& step) {
+                                                    std::vector<uint32_t>& counts, Step&& step,
+                                                    bool device_plan = false) {
         const auto t0 = std::chrono::steady_clock::now();
         FlatScene flat = scene.flatten();
         rt_scene rs = flat.view();
@@ -419,7 +422,17 @@ struct GpuRenderer : Renderer {
         (void)collect();
         counts.assign(npx, 0u);
         std::vector<double> err(npx);
-        for (;;) {
+        while (device_plan) {
+            uint64_t active = 0, traced = 0;
+            chk(rt_progressive_refine(x.c, tolerance, (uint32_t)spp, nullptr, &active, &traced), "rt_progressive_refine");
+            if (active == 0) {
+                (void)collect();   // a half-count snapshot above 2.0 is not the image's
+                chk(rt_progressive_counts(x.c, counts.data()), "rt_progressive_counts");
+                break;
+            }
+            step((size_t)active, traced);
+        }
+        while (!device_plan) {
             chk(rt_progressive_error_async(x.c, x.err, nullptr), "rt_progressive_error_async");
             (void)collect();   // a half-count snapshot above 2.0 is not the image's
             chk(rt_memcpy_d2h(x.c, err.data(), x.err, npx * sizeof(double)), "rt_memcpy_d2h");

@@ -135,7 +135,7 @@ EXPORTED = [
     "rt_memcpy_d2h", "rt_last_error", "rt_version", "rt_render_split_async", "rt_split_plan",
     "rt_progressive_bytes", "rt_progressive_begin", "rt_progressive_extend_async", "rt_progressive_end",
     "rt_progressive_extend_map_async", "rt_progressive_snapshot_map_async", "rt_progressive_counts",
-    "rt_progressive_error_async", "rt_progressive_map_plan",
+    "rt_progressive_error_async", "rt_progressive_map_plan", "rt_progressive_refine", "rt_progressive_refine_items",
 ]
 
 _lib = None
@@ -206,6 +206,8 @@ def load_library(path=None):
     lib.rt_progressive_counts.argtypes = [vp, P(u32)]
     lib.rt_progressive_error_async.argtypes = [vp, vp, vp]
     lib.rt_progressive_map_plan.argtypes = [u64, P(u32), P(u32), u32, P(u32), P(u64), P(u32), u64]
+    lib.rt_progressive_refine.argtypes = [vp, f64, u32, vp, P(u64), P(u64)]
+    lib.rt_progressive_refine_items.argtypes = [vp, P(u32), P(u64), P(u32), u64]
     lib.rt_context_collect.argtypes = [vp, vp, P(RtStats)]
     lib.rt_device_alloc.argtypes = [vp, ctypes.c_size_t, P(vp)]
     lib.rt_device_free.argtypes = [vp, vp]

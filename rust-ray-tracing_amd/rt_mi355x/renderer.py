@@ -20,9 +20,13 @@ from . import abi
 class RenderStat:
     """renderer.rs:11-34 (+ the GPU work counters)."""
 
-    def __init__(self, duration, pixels_rendered, kernel_ms=0.0, samples=0, ray_segments=0, range_error=False):
+    def __init__(self, duration, pixels_rendered, kernel_ms=0.0, samples=0, ray_segments=0, range_error=False,
+                 bounce_iters=0):
         # range_error (GpuRenderer.progressive only): a pixel channel exceeded 2.0 at this step (RT_ERR_RANGE)
         self.range_error = bool(range_error)
+        # bounce_iters (GpuRenderer.adaptive only): rt_stats.bounce_iters summed over the run, a pixel's K once per
+        # reduction of that pixel
+        self.bounce_iters = int(bounce_iters)
         self._duration = float(duration)
         self._pixels = int(pixels_rendered)
         self._pps = self._pixels / self._duration if self._duration > 0 else 0.0
@@ -75,9 +79,15 @@ def check_schedule(schedule):
     return counts
 
 
-def check_adaptive(spp_min, spp_max, tolerance):
+ADAPTIVE_PLANS = ("host", "device")
+
+
+def check_adaptive(spp_min, spp_max, tolerance, plan="host"):
     """GpuRenderer.adaptive's arguments checked before any GPU call: 1 <= spp_min <= spp_max, a tolerance that is
-    a number (not NaN).  Returns (spp_min, spp_max, tolerance) as (int, int, float)."""
+    a number (not NaN), a plan that is "host" or "device".  Returns (spp_min, spp_max, tolerance) as
+    (int, int, float)."""
+    if plan not in ADAPTIVE_PLANS:
+        raise ValueError(f"unknown plan {plan!r} (one of {list(ADAPTIVE_PLANS)})")
     for name, n in (("spp_min", spp_min), ("spp_max", spp_max)):
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
             raise ValueError(f"{name} must be an int, not {n!r}")
@@ -108,6 +118,7 @@ class ProgressiveSession:
         tr = tile_range if tile_range is not None else abi.RtTileRange(0, 1, cam.image_height, 0, cam.image_width)
         self.npx = tr.row_count * tr.col_count
         self._counts = np.zeros(self.npx, dtype=np.uint32)
+        self._stale = False   # refine() moved counts on the device since _counts was read
         abi.check(self.lib, self.lib.rt_progressive_begin(renderer.ctx, ctypes.byref(cam), max_bounces, spp_capacity,
                                                           renderer.seed, renderer.flags, ctypes.byref(tr), max_bytes))
         self._open = True
@@ -116,16 +127,21 @@ class ProgressiveSession:
     @property
     def counts(self):
         """Samples traced so far per pixel: np.uint32[n] (a copy)."""
+        if self._stale and self._open:
+            self._refresh()
         return self._counts.copy()
 
     @property
     def done(self):
         """Samples every pixel holds: the minimum over the pixels (a uniform session: its sample count)."""
+        if self._stale and self._open:
+            self._refresh()
         return int(self._counts.min())
 
     def _refresh(self):
         abi.check(self.lib, self.lib.rt_progressive_counts(self.renderer.ctx,
                                                            self._counts.ctypes.data_as(ctypes.POINTER(abi.u32))))
+        self._stale = False
 
     def _map_argument(self, counts, what):
         a = np.ascontiguousarray(counts)
@@ -204,6 +220,41 @@ class ProgressiveSession:
         finally:
             lib.rt_device_free(ctx, d_err)
         return (err, st) if stats else err
+
+    def refine(self, tolerance, spp_max, stream=None):
+        """rt_progressive_refine: one step of the doubling policy, selected and planned on the device.  Returns
+        (n_active, n_samples): the pixels whose estimate was above `tolerance` and that went to
+        min(2 * count, spp_max), and the samples enqueued for them; n_active == 0: converged, nothing traced.  The
+        call waits for the selection (one small readback), not for the tracing: collect() follows."""
+        if not self._open:
+            raise RuntimeError("the progressive session is closed")
+        na, ns = abi.u64(), abi.u64()
+        abi.check(self.lib, self.lib.rt_progressive_refine(self.renderer.ctx, float(tolerance), int(spp_max), stream,
+                                                           ctypes.byref(na), ctypes.byref(ns)))
+        self._stale = True
+        return na.value, ns.value
+
+    def refine_items(self):
+        """rt_progressive_refine_items: (samples_per_item, items np.uint32[n, 4] of pixel, first, end, 0) of the
+        item table the last refine() built on the device; (0, empty) when it selected nothing."""
+        if not self._open:
+            raise RuntimeError("the progressive session is closed")
+        lib, ctx, U32P = self.lib, self.renderer.ctx, ctypes.POINTER(abi.u32)
+        s, n = abi.u32(), abi.u64()
+        abi.check(lib, lib.rt_progressive_refine_items(ctx, ctypes.byref(s), ctypes.byref(n), None, 0))
+        items = np.zeros((n.value, 4), dtype=np.uint32)
+        if n.value:
+            abi.check(lib, lib.rt_progressive_refine_items(ctx, ctypes.byref(s), ctypes.byref(n),
+                                                           items.ctypes.data_as(U32P), n.value))
+        return s.value, items
+
+    def collect(self, stream=None):
+        """rt_context_collect: wait for the work enqueued on `stream` and return its RtStats (a channel above 2.0 in
+        one of its reductions is not an error here)."""
+        st = abi.RtStats()
+        abi.check(self.lib, self.lib.rt_context_collect(self.renderer.ctx, stream, ctypes.byref(st)),
+                  allow=(abi.RT_ERR_RANGE,))
+        return st
 
     def close(self):
         if self._open:
@@ -355,23 +406,31 @@ class GpuRenderer(Renderer):
                 yield n, img, RenderStat(dt, cam.image_width * cam.image_height, st.kernel_ms, st.samples,
                                          st.ray_segments, range_error=rc == abi.RT_ERR_RANGE)
 
-    def adaptive(self, max_bounces, spp_min, spp_max, tolerance, scene, camera):
+    def adaptive(self, max_bounces, spp_min, spp_max, tolerance, scene, camera, plan="host"):
         """Adaptive sampling: every pixel gets spp_min samples, then the pixels whose error estimate
         (ProgressiveSession.error) is above `tolerance` double their count, up to spp_max, until none is left.
         Returns (image HxWx3 uint8, counts HxW uint32, RenderStat); pixel p of the image equals render()'s at
-        spp = counts[p], and stat.samples is the total traced (counts.sum()).  The live path only."""
-        spp_min, spp_max, tolerance = check_adaptive(spp_min, spp_max, tolerance)   # before any GPU call
+        spp = counts[p], and stat.samples is the total traced (counts.sum()).  The live path only.
+        plan: "host" estimates the whole frame, selects in numpy and sends a map per step; "device" keeps the
+        estimate, the selection and the item table on the GPU (ProgressiveSession.refine) and reads the counts
+        back once, at the end.  Same counts, same image."""
+        spp_min, spp_max, tolerance = check_adaptive(spp_min, spp_max, tolerance, plan)   # before any GPU call
         t0 = time.perf_counter()
         cam = camera.abi if hasattr(camera, "abi") else camera
-        ms, samples, segs = 0.0, 0, 0
+        ms, samples, segs, iters = 0.0, 0, 0, 0
 
         def add(st):
-            nonlocal ms, samples, segs
+            nonlocal ms, samples, segs, iters
             ms, samples, segs = ms + st.kernel_ms, samples + st.samples, segs + st.ray_segments
+            iters += st.bounce_iters
 
         with self.begin_progressive(max_bounces, spp_max, scene, cam) as session:
             add(session.extend(spp_min, image=False))
-            while True:
+            if plan == "device":
+                while session.refine(tolerance, spp_max)[0]:   # each step waits for its selection only
+                    pass
+                add(session.collect())   # a half-count reduction above 2.0 is not the image's
+            while plan == "host":
                 err, st = session.error(stats=True)
                 add(st)
                 counts = session.counts
@@ -387,4 +446,4 @@ class GpuRenderer(Renderer):
         if rc == abi.RT_ERR_RANGE:
             raise abi.RtError(rc, "a pixel channel exceeded 2.0 (reference: Color::to_u8_array panics)")
         h, w = cam.image_height, cam.image_width
-        return rgb.reshape(h, w, 3), counts.reshape(h, w), RenderStat(dt, w * h, ms, samples, segs)
+        return rgb.reshape(h, w, 3), counts.reshape(h, w), RenderStat(dt, w * h, ms, samples, segs, bounce_iters=iters)

@@ -10,9 +10,12 @@ tools/progressive_ab.py: a warm-up of each side, then the sides alternating, the
 (b) An adaptive run (GpuRenderer.adaptive's policy, 16 -> 512 spp on config C's frame, the tolerance at the median
     of the first error estimate) against a uniform session extended to 512 spp.  Reports the samples traced, the
     steps, kernel_ms and wall time of both, and where the adaptive run's kernel time goes (tracing steps, error
-    estimates, the final image).
+    estimates, the final image).  A third leg (d) runs the same policy planned on the device
+    (rt_progressive_refine); its counts must equal the host-driven leg's.  A refine call returns when its selection
+    is known and its tracing is enqueued, so the wall time of the call is the step's estimate, selection and
+    readback, and the step's kernel_ms less that is its tracing.
 
-The evidence for DESIGN.md §4 "Per-pixel counts" (profiles/adaptive.txt).
+The evidence for DESIGN.md §4 "Per-pixel counts" (profiles/adaptive.txt, profiles/adaptive_device.txt).
 
     python tools/adaptive_ab.py [--reps 7] [--parts a,b] [--out FILE]
 """
@@ -113,12 +116,46 @@ def gain(say, lib, flat, depth, reps):
                 _, _, st, _ = s.snapshot()
                 out["image"] = st.kernel_ms
                 out["wall"] = (time.perf_counter() - t0) * 1e3
-                out["classes"] = np.unique(s.counts, return_counts=True)
+                out["counts"] = s.counts
+                out["classes"] = np.unique(out["counts"], return_counts=True)
             out["ms"] = out["trace"] + out["error"] + out["image"]
             return out
 
-        res = alternate([("u", uniform), ("a", adaptive)], reps)
-        u, a = res["u"], res["a"]
+        def device():
+            out = {"trace": 0.0, "error": 0.0, "image": 0.0, "samples": 0, "steps": [], "active": []}
+            with r.begin_progressive(depth, SPP_MAX, flat, cam) as s:
+                t0 = time.perf_counter()
+                st = s.extend(SPP_MIN, image=False)
+                out["trace"] += st.kernel_ms
+                out["samples"] += st.samples
+                out["steps"].append(st.kernel_ms)
+                while True:
+                    t1 = time.perf_counter()
+                    n_active, _ = s.refine(tol, SPP_MAX)
+                    select_ms = (time.perf_counter() - t1) * 1e3
+                    st = s.collect()
+                    if n_active == 0 and st.kernel_ms == 0.0:   # every candidate at the cap: nothing ran
+                        break
+                    select_ms = min(select_ms, st.kernel_ms)
+                    out["error"] += select_ms
+                    if n_active == 0:
+                        break
+                    out["trace"] += st.kernel_ms - select_ms
+                    out["samples"] += st.samples
+                    out["steps"].append(st.kernel_ms - select_ms)
+                    out["active"].append(n_active)
+                _, _, st, _ = s.snapshot()
+                out["image"] = st.kernel_ms
+                out["wall"] = (time.perf_counter() - t0) * 1e3
+                out["counts"] = s.counts
+                out["classes"] = np.unique(out["counts"], return_counts=True)
+            out["ms"] = out["trace"] + out["error"] + out["image"]
+            return out
+
+        res = alternate([("u", uniform), ("a", adaptive), ("d", device)], reps)
+        u, a, d = res["u"], res["a"], res["d"]
+        assert all(np.array_equal(x["counts"], y["counts"]) for x, y in zip(a, d)), "device and host counts differ"
+        assert d[0]["samples"] == a[0]["samples"] and d[0]["active"] == a[0]["active"]
         say(f"(b) C {w}x{h} f32, {SPP_MIN} -> {SPP_MAX} spp, tolerance {tol:.6g} (the median of the first error)")
         say(f"    (u) uniform session to {SPP_MAX}     kernel {med([x['ms'] for x in u]):9.3f} ms  "
             f"wall {med([x['wall'] for x in u]):9.3f} ms  samples {u[0]['samples']}")
@@ -133,6 +170,16 @@ def gain(say, lib, flat, depth, reps):
         say(f"    samples a/u {a[0]['samples'] / u[0]['samples']:.3f}   kernel a/u "
             f"{med([x['ms'] for x in a]) / med([x['ms'] for x in u]):.3f}   wall a/u "
             f"{med([x['wall'] for x in a]) / med([x['wall'] for x in u]):.3f}")
+        say(f"    (d) device-planned, {len(d[0]['steps']) - 1} refinement steps  kernel {med([x['ms'] for x in d]):9.3f} ms  "
+            f"wall {med([x['wall'] for x in d]):9.3f} ms  samples {d[0]['samples']}  (counts equal to (a)'s)")
+        say(f"        kernel ms: tracing {med([x['trace'] for x in d]):.3f}, estimates and selection "
+            f"{med([x['error'] for x in d]):.3f}, final image {med([x['image'] for x in d]):.3f}")
+        say("        per step (first: the uniform one): " +
+            ", ".join(f"{med([x['steps'][i] for x in d]):.3f}" for i in range(len(d[0]['steps']))))
+        say(f"        active pixels per refinement step: {d[0]['active']}")
+        for name, other in (("u", u), ("a", a)):
+            say(f"    kernel d/{name} {med([x['ms'] for x in d]) / med([x['ms'] for x in other]):.3f}   wall d/{name} "
+                f"{med([x['wall'] for x in d]) / med([x['wall'] for x in other]):.3f}")
     finally:
         r.close()
 
