@@ -39,6 +39,7 @@ __device__ __forceinline__ SphGroup<T> load_group(const __attribute__((address_s
 }
 
 typedef float f2 __attribute__((ext_vector_type(2)));
+typedef float F4 __attribute__((ext_vector_type(4)));
 struct Q4 { uint32_t x, y, z, w; };
 
 // One top group of the general sweep (kBoxFloats floats; layout at rt_formats.hpp).
@@ -92,8 +93,9 @@ template <typename T> struct KParams {
                                // their 4 records {r^2 of the pairs (fp32 rays), 4 scene indices} (inline_stream)
     const float* ftop;
     const float* fsup;         // super boxes (4 clusters each), 4 per group
-    const float* fmeg;         // mega boxes (4 supers each), 4 per group; n_mg groups, 0: no mega level
-    uint32_t n_mg;
+    const float* rflat;        // fp32 rays: one {cx, cy, cz, r^2} record per slot, ridx's order and length (pack_flat;
+                               // fp64: NULL).  At the offset of the scene-frame mega boxes no kernel read any more
+    uint32_t n_mg;             // mega groups (4 megas each), 0: no mega level
     // MEGA kernels: the sphere filter in cluster-local frames (pack_local): filter groups with centres
     // relative to their cluster's centre, inline with each cluster's records (rt_layout.hpp's inline_stream: the
     // scene indices, and the frame {Cx, Cy, Cz, Rc} / {r2max, 1/r2min} in the r^2 words of records 0 / 1)
@@ -183,9 +185,11 @@ enum WorkCounter : uint32_t {
     kWCExact = 4,   // camera sweep: exact tests from the camera-origin table (8 FLOP in T each)
     kNWork = 5,
 };
-constexpr int kWorkSlot = 11;   // shard slots 11..15 (kstats uses 3..10)
+constexpr int kWorkSlot = 11;   // shard slots 11..15 (kstats uses 3..10 and 17..21: kstat_slot, rt_experiments.hpp)
 constexpr int kDirectSkySlot = 16;   // samples of pixels finished at claim time (rt_stats.direct_sky_samples)
 static_assert(kWorkSlot + kNWork <= kDirectSkySlot && kDirectSkySlot < kSegStride, "counters past the shard's slots");
+static_assert(kKstatSlot >= 3 && kKstatSlot + kNKstat1 <= kWorkSlot && kKstatSlot2 > kDirectSkySlot &&
+              kKstatSlot2 + (kNKstat - kNKstat1) <= kSegStride, "kstats counters over another counter's slot");
 // u64: a wave of a persistent launch can run billions of tests (config E: ~1.3M filter groups per
 // wave; spp up to 2^20 on a 4K frame is ~3000x that), past a u32.
 __shared__ unsigned long long g_work[4][kNWork];

@@ -18,6 +18,7 @@
                             defined(RT_EXP_DUP_SCATTER) || defined(RT_EXP_DUP_SWEEP) || defined(RT_EXP_DUP_CLBOX) ||   \
                             defined(RT_EXP_DUP_FILTER) || defined(RT_EXP_DUP_SUPBOX) || defined(RT_EXP_DUP_MEGABOX) || \
                             defined(RT_EXP_DUP_PLIST) || defined(RT_EXP_DUP_REPLAY) || defined(RT_EXP_DUP_REDUCE) ||   \
+                            defined(RT_EXP_DUP_FLUSH) ||                                                                \
                             defined(RT_EXP_TIMELINE) || \
                             defined(RT_KSTATS))
 #error "an experiment macro in the product build"
@@ -54,9 +55,14 @@ constexpr uint32_t kLMapCap = RT_EXP_LMAP_CAP;
 constexpr uint32_t kLMapCap = 512;
 #endif
 
-// Instrumented build only (make kstats): wave-level event counters, written to shard slots 3..10.
+// The instrumented build's (make kstats) wave-level event counters and their shard slots: counters 0..kNKstat1-1
+// at slots kKstatSlot.., the rest (the flush scope counters of nearest_hit) at kKstatSlot2..; kstat_slot() is the
+// one map, for the kernels' write-out and rt_context_collect's read-back (rt_common.hpp checks it against the
+// shard's other slots).
+constexpr int kNKstat = 13, kNKstat1 = 8, kKstatSlot = 3, kKstatSlot2 = 17;
+constexpr int kstat_slot(int i) { return i < kNKstat1 ? kKstatSlot + i : kKstatSlot2 + (i - kNKstat1); }
 #ifdef RT_KSTATS
-__shared__ unsigned long long g_kst[4][8];
+__shared__ unsigned long long g_kst[4][kNKstat];
 __device__ __forceinline__ void kstat(uint32_t i, uint32_t n = 1) {
     const unsigned long long ex = __builtin_amdgcn_read_exec();
     if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(ex)) atomicAdd(&g_kst[threadIdx.x >> 6][i], (unsigned long long)n);

@@ -155,7 +155,7 @@ static int stage_reserve(PinnedStage& g, size_t n) {
 // tables build_cam_table fills at a launch.  The camera tables depend only on the scene, the camera
 // centre, the scalar mode and RT_FILTER_OFF: a launch with the same key reuses them (bench frames, shards).
 template <typename T> struct DeviceScene {
-    DeviceBuffer sph, cen, fsph, rsph, rfsph, top, sup, meg, lfs, lbx[4], clus, mats;
+    DeviceBuffer sph, cen, fsph, rsph, rfsph, rflat, top, sup, lfs, lbx[4], clus, mats;
     DeviceBuffer cam, camf, camx, cull, cullc;   // camera-origin, camera filter, per-sphere, cone-cull, per-cluster
     TableConsts k;
     struct CamKey { bool valid = false; double center[3] = {0, 0, 0}; uint32_t scalar = 0, off = 0; } camkey;
@@ -166,8 +166,8 @@ template <typename T> static int upload_scene(DeviceScene<T>& d, const SceneTabl
     auto up = [&](DeviceBuffer& dst, const auto& v) { if (rc == RT_OK) rc = upload(dst, v); };
     auto room = [&](DeviceBuffer& dst, size_t bytes) { if (rc == RT_OK) rc = reserve(dst, bytes); };
     up(d.sph, t.sph); up(d.cen, t.cen); up(d.fsph, t.fsph);
-    up(d.rsph, t.rsph); up(d.rfsph, t.rfsph);
-    up(d.top, t.top); up(d.sup, t.sup); up(d.meg, t.meg);
+    up(d.rsph, t.rsph); up(d.rfsph, t.rfsph); up(d.rflat, t.rflat);
+    up(d.top, t.top); up(d.sup, t.sup);   // t.meg stays on the host: the mega kernels read the local levels (lbx)
     up(d.lfs, t.lfs);
     for (int lv = 0; lv < 4; ++lv) up(d.lbx[lv], t.lbx[lv]);
     up(d.clus, t.clus); up(d.mats, t.mats);
@@ -469,7 +469,7 @@ static void scene_params(rt_context* c, KParams<T>& p) {
     p.rfsph = (const float*)d.rfsph.p;
     p.ftop = (const float*)d.top.p;
     p.fsup = (const float*)d.sup.p;
-    p.fmeg = (const float*)d.meg.p;
+    p.rflat = (const float*)d.rflat.p;
     p.n_mg = n.n_mg;
     p.lfsph = (const float*)d.lfs.p;
     p.lclb = (const float*)d.lbx[0].p;
@@ -1493,15 +1493,20 @@ extern "C" int rt_context_collect(rt_context* c, void* stream, rt_stats* out) {
     if (c->have_first) HIPCHK(hipEventElapsedTime(&ms, c->ev_first, c->ev_last));
     HIPCHK(hipMemset(c->segs.p, 0, segs.size() * sizeof(unsigned long long)));
     HIPCHK(hipMemset(c->err.p, 0, 16));
-    uint64_t total = 0, slots = 0, iters = 0, dsky = 0, kst[8] = {0, 0, 0, 0, 0, 0, 0, 0}, work[kNWork] = {};
+    uint64_t total = 0, slots = 0, iters = 0, dsky = 0, kst[kNKstat] = {}, work[kNWork] = {};
     for (int i = 0; i < kSegShards; ++i)
-        for (int j = 0; j < 8; ++j) kst[j] += segs[(size_t)i * kSegStride + 3 + j];
-    if (kst[0] | kst[1] | kst[2] | kst[3])   // instrumented build (make kstats) only
+        for (int j = 0; j < kNKstat; ++j) kst[j] += segs[(size_t)i * kSegStride + kstat_slot(j)];
+    if (kst[0] | kst[1] | kst[2] | kst[3]) {   // instrumented build (make kstats) only
         fprintf(stderr, "rt_kstats: general taken_groups %llu sweeps %llu clusters %llu top_groups %llu  camera "
                 "candidates %llu sweeps %llu  finish_pixel %llu  filter_lanes_passing %llu\n",
                 (unsigned long long)kst[0], (unsigned long long)kst[1], (unsigned long long)kst[4],
                 (unsigned long long)kst[5], (unsigned long long)kst[2], (unsigned long long)kst[3],
                 (unsigned long long)kst[6], (unsigned long long)kst[7]);
+        // ... and the flush scope of the fp32 scene-frame sweeps (counters 8..12)
+        fprintf(stderr, "rt_kstats: flush steps_per_super_max %llu steps_per_sweep_max %llu lanes_two_supers %llu "
+                "lanes_any %llu lanes_two_pairs %llu\n", (unsigned long long)kst[8], (unsigned long long)kst[9],
+                (unsigned long long)kst[10], (unsigned long long)kst[11], (unsigned long long)kst[12]);
+    }
     for (int i = 0; i < kSegShards; ++i) {
         total += segs[(size_t)i * kSegStride];
         slots += segs[(size_t)i * kSegStride + 1];

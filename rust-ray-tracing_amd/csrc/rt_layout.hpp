@@ -673,6 +673,21 @@ static std::vector<float> inline_stream(const std::vector<float>& src, size_t n_
     return rx;
 }
 
+// Flat slot records for the per-lane exact tests of the fp32 scene-frame kernels (nearest_hit's flush): one
+// aligned 16-byte record {cx, cy, cz, r^2} per slot, n_slots of them (ridx's length: record i and ridx[i] are the
+// same slot), so a lane gathers its sphere in one load at 16 x slot.  The words are copied from the fp32 slot-order
+// exact groups (pack_sweep's rgrp): the centres the filter groups of the cluster blocks hold and the r^2 of their
+// records (inline_stream), bit for bit; a dummy slot is {0, 0, 0, -inf} there and here, and so are the slots past
+// the last cluster.
+static std::vector<float> pack_flat(const std::vector<float>& rg32, size_t n_slots) {
+    std::vector<float> fl((size_t)4 * n_slots, 0.0f);
+    const size_t ns = (rg32.size() / 16 - 1) * 4;   // without the dummy group
+    for (size_t i = 0; i < n_slots; ++i)
+        for (int f = 0; f < 4; ++f)
+            fl[4 * i + f] = i < ns ? rg32[16 * (i / 4) + 8 * ((i % 4) / 2) + 2 * f + (i % 2)] : (f == 3 ? -INFINITY : 0.0f);
+    return fl;
+}
+
 // ---- the scene image ----
 // The constants the kernels take with one precision's tables.
 struct TableConsts {
@@ -691,7 +706,10 @@ template <typename T> struct SceneTables {
     std::vector<float> fsph;               // fp32 filter stream (pack_filter)
     std::vector<T> rsph;                   // general sweep: slot-order exact groups (pack_sweep)
     std::vector<float> rfsph;              // slot-order filter groups, inline layout (inline_stream)
-    std::vector<float> top, sup, meg;      // cluster boxes, super boxes (4 clusters each), mega boxes (big scenes only)
+    std::vector<float> rflat;              // fp32 rays: one {cx, cy, cz, r^2} record per slot (pack_flat)
+    std::vector<float> top, sup;           // cluster boxes, super boxes (4 clusters each)
+    std::vector<float> meg;                // scene-frame mega boxes (big scenes only).  Host only: non-empty marks a mega
+                                           // level (n_mg, the local levels below) and feeds pack_mega_tiers; never uploaded
     std::vector<float> lfs;                // cluster-local filter groups, inline layout (big scenes only)
     std::vector<float> lbx[4];             // local box levels: cluster boxes, supers, megas, gigas (big scenes only)
     std::vector<double> clus;              // cluster (then super) bounding spheres {C, R} (cluster_bounds)
@@ -735,6 +753,7 @@ static void build_tables(const rt_scene* s, const SweepLayout& L, const SceneIma
     const std::vector<float>* rg32 = nullptr;
     if constexpr (sizeof(T) == 4) rg32 = &t.rsph;
     t.rfsph = inline_stream(rf, L.n_xg, rg32, im.ridx, nullptr);
+    if constexpr (sizeof(T) == 4) t.rflat = pack_flat(t.rsph, im.ridx.size());
     if (!t.meg.empty()) {   // the mega kernels' local streams and box levels
         std::vector<float> lf, lr, q;
         pack_local(t.cen, L, t.top, lf, lr, q);

@@ -516,45 +516,48 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
         uint32_t n_box = 0, n_filt = 0, n_exact = 0;
         // fp32, scene-frame filter groups (not MEGA): the exact tests behind the filter run per lane.  The
         // filter leaves each lane a 16-bit mask of its own passing spheres per walked cluster (bit 15 - s:
-        // slot s), two clusters to a word; after the walked clusters of a super every lane with a bit set
-        // takes one of its spheres per step, gathers that slot's record from its cluster's block of the
-        // filter stream (centres in groups 0..3, the same fp32 values as the exact stream's, pack_filter /
-        // pack_sweep; r^2 and the scene index in the records behind them, inline_stream) and runs the
-        // reference's test for that one sphere (objects.rs:252-257; SCALAR: :217-222).  The wave takes as
-        // many steps as its busiest lane has candidates, not one pair-step per sphere pair that any lane
-        // passes.  The nearest hit does not depend on the visiting order (hit_update), and the super's
-        // cluster boxes were all tested before its first cluster was walked, so nothing waits for these
-        // hits before the next super's box test.  Every slot of a walked cluster lies inside its block,
-        // dummies too (their filter D is -inf: never a candidate).
-        // blk: the block of the even cluster of the pair; cand: bits 0..15 that cluster, 16..31 the next.
-        auto flush = [&](cptr<float> blk, uint32_t cand) {
+        // slot s), two clusters to a word, so bit b of the word is slot b ^ 15 of the 32 slots of its cluster
+        // pair (a half-super).  After the pair's last walked cluster every lane with a bit set takes one of its
+        // spheres per step: the slot's record from the flat slot table (pack_flat: one aligned {cx, cy, cz, r^2}
+        // per slot, the same fp32 values as the streams'; the cluster slots from offset 0, pair h of super sup at
+        // byte 1024 sup + 512 h) in one 16-byte load, the scene index from ridx at a quarter of the offset, and
+        // the reference's test for that one sphere (objects.rs:252-257; SCALAR: :217-222).  Per step: find the
+        // bit, clear it, one xor-add and one shift for the two offsets.  The wave takes as many steps as its
+        // busiest lane has candidates in the pair, not one pair-step per sphere pair that any lane passes.  The
+        // nearest hit does not depend on the visiting order (hit_update), and the super's cluster boxes were all
+        // tested before its first cluster was walked, so nothing waits for these hits before the next super's
+        // box test.  Only lanes with a bit set load, and every slot of a walked cluster, dummies too (their
+        // filter D is -inf: never a candidate), has its record and its ridx word.
+        // Keeping the candidates pending across pairs and supers, so that lanes with candidates in different
+        // supers step together, was measured and not kept (profiles/r09/flush_scope_kstats.txt): 2.96 steps
+        // per sweep instead of 3.42, but 4 % more filter groups (a deferred hit culls no cluster box) and a
+        // conflict test per walked pair: slower than this by 1.1 % of the frame.
+        // ofs: the pair's byte offset in the table (wave-uniform); cand: bits 0..15 its even cluster, 16..31 the odd.
+        auto flush = [&](uint32_t ofs, uint32_t cand) {
             if constexpr (sizeof(T) == 4) {
+                const cptr<char> fl = (cptr<char>)__builtin_assume_aligned(qa.rflat, 16) + 64u * nxg;
+                const cptr<char> ri = (cptr<char>)__builtin_assume_aligned(qa.ridx, 16) + 16u * nxg;
                 while (__ballot(cand != 0u) != 0ull) {
                     KSTAT(0);
                     ++n_exact;
                     if (cand != 0u) {
                         const uint32_t b = (uint32_t)__builtin_ctz(cand);
                         cand &= cand - 1u;
-                        const uint32_t s = (b & 15u) ^ 15u;    // the slot in its cluster
-                        const uint32_t cb = (b & 16u) * 6u;    // the odd cluster's block: 96 words on
-                        // group s / 4, pair (s / 2) % 2, half s % 2: the centre at 16 g + 8 q + h (+ 0, 2, 4),
-                        // r^2 at 64 + 8 g + 2 q + h, the scene index 4 words behind it
-                        const uint32_t ic = cb + (((s & 14u) << 2) | (s & 1u));
-                        const uint32_t ir = cb + (((s & 12u) << 1) | (s & 3u));
-                        const float cx = blk[ic], cy = blk[ic + 2u], cz = blk[ic + 4u], r2 = blk[64u + ir];
-                        uint32_t si = ((cptr<uint32_t>)blk)[68u + ir];
-                        const float ocx = o.x - cx, ocy = o.y - cy, ocz = o.z - cz;   // :252
+                        const uint32_t at = ofs + ((b ^ 15u) << 4);   // 16 x the slot among the cluster slots
+                        const F4 rec = *(cptr<F4>)(fl + at);
+                        uint32_t si = *(cptr<uint32_t>)(ri + (at >> 2));
+                        const float ocx = o.x - rec.x, ocy = o.y - rec.y, ocz = o.z - rec.z;   // :252
                         float hb, disc;
                         if constexpr (SCALAR) {                                       // objects.rs:217-222
                             hb = (ocx * d.x + ocy * d.y) + ocz * d.z;
-                            const float c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - r2;
+                            const float c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - rec.w;
                             disc = hb * hb - a * c;
                         } else {
                             hb = __builtin_fmaf(ocz, d.z, __builtin_fmaf(ocy, d.y, ocx * d.x));              // :255
-                            const float c = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, ocx * ocx)) - r2;   // :256
+                            const float c = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, ocx * ocx)) - rec.w;   // :256
                             disc = __builtin_fmaf(hb, hb, -a * c);                                           // :257
                         }
-                        // the index load stays with the others (sunk into the branch it would be a second
+                        // the index load stays with the record's (sunk into the branch it would be a second
                         // dependent round trip per step)
                         asm volatile("" : "+v"(si));
                         if (cand_f(hb, disc)) hit(hb, disc, si);
@@ -562,6 +565,17 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
                 }
             }
         };
+#ifdef RT_KSTATS
+        // flush scope (profiles/r09/flush_scope_kstats.txt): the lane's candidates in the super being walked and
+        // over the sweep, its supers and its pairs with any
+        constexpr bool kInlK = sizeof(T) == 4 && !MEGA && !CAMT;
+        uint32_t ks_cur = 0u, ks_tot = 0u, ks_sup = 0u, ks_pair = 0u;
+        auto wave_max = [](uint32_t v) -> uint32_t {
+            uint32_t m = 0u;
+            while (__ballot(v > m) != 0ull) ++m;
+            return m;
+        };
+#endif
         // the always-exact groups; fp32 skips a pair of dummies at the end (the ground sphere's group
         // at config C: ground + 3 dummies); in fp64 the variable pair mask costs VGPR spills at W4
         for (uint32_t g = 0; g < nxg; ++g) {
@@ -585,7 +599,7 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
                 mask = lmask(load_lbox((cptr<float>)__builtin_assume_aligned(qa.lclb, 64), sup));
             }
             else mask = box_mask(load_box(ft, sup), B0, B1, B2, B3, B4, btf());
-            uint32_t c01 = 0u, c23 = 0u;   // kInl: the lane's candidates in clusters 0, 1 and 2, 3 of the super
+            uint32_t cpr = 0u;   // kInl: the lane's candidates in the cluster pair being walked (clusters 0, 1 or 2, 3)
             while (mask != 0u) {
                 const uint32_t kj = (uint32_t)__builtin_ctz(mask);
                 const uint32_t kc = 4u * sup + kj;   // cluster
@@ -666,16 +680,27 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
                     }
                 });
                 if constexpr (kInl) {
-                    if (kj < 2u) c01 |= ~fm << (16u * kj);
-                    else c23 |= ~fm << (16u * kj - 32u);
+                    cpr |= ~fm << (16u * (kj & 1u));
+                    // the pair's last walked cluster (mask: the super's clusters still to walk)
+                    if ((mask & (kj < 2u ? 3u : 12u)) == 0u) {
+#ifdef RT_KSTATS
+                        ks_cur += (uint32_t)__builtin_popcount(cpr);
+                        ks_pair += cpr != 0u ? 1u : 0u;
+#endif
+                        flush(1024u * sup + 512u * (kj >> 1), cpr);
+                        cpr = 0u;
+                    }
                 }
             }
-            if constexpr (sizeof(T) == 4 && !MEGA) {
-                KSTAT(7, (uint32_t)__popcll(__ballot((c01 | c23) != 0u)));   // lanes with a candidate in this super
-                const cptr<float> sb = ff + 16u * nxg + 384u * sup;
-                flush(sb, c01);
-                flush(sb + 192u, c23);
+#ifdef RT_KSTATS
+            if constexpr (kInlK) {
+                KSTAT(7, (uint32_t)__popcll(__ballot(ks_cur != 0u)));   // lanes with a candidate in this super
+                KSTAT(8, wave_max(ks_cur));                             // (c): steps of one flush per walked super
+                ks_tot += ks_cur;
+                ks_sup += ks_cur != 0u ? 1u : 0u;
+                ks_cur = 0u;
             }
+#endif
         };
         // The top level is the super boxes, or (MEGA: scenes with more than 8 super groups, config E)
         // the mega boxes; chunks of 8 top groups (32 boxes) give a 32-bit wave mask of the passing
@@ -784,6 +809,14 @@ __device__ __forceinline__ int nearest_hit(const KParams<T>& p, const V3<T>& o, 
                     walk_super(nd);
                 }
             }
+#ifdef RT_KSTATS
+            if constexpr (kInlK) {
+                KSTAT(9, wave_max(ks_tot));                                   // (d): steps of one flush per sweep
+                KSTAT(10, (uint32_t)__popcll(__ballot(ks_sup >= 2u)));        // lanes with candidates in two or more supers
+                KSTAT(11, (uint32_t)__popcll(__ballot(ks_sup >= 1u)));        // lanes with any candidate
+                KSTAT(12, (uint32_t)__popcll(__ballot(ks_pair >= 2u)));       // lanes with candidates in two or more pairs
+            }
+#endif
         }
         work_add(kWBox, n_box);
         work_add(kWFilt, n_filt);

@@ -45,7 +45,7 @@
     if (lane == 0) { wcount[wave][0] = 0; wcount[wave][1] = 0; wcount[wave][2] = 0; wcount[wave][3] = 0; }
     if (lane < kNWork) g_work[wave][lane] = 0ull;
 #ifdef RT_KSTATS
-    if (lane < 8) g_kst[wave][lane] = 0;
+    if (lane < kNKstat) g_kst[wave][lane] = 0;
 #endif
     if constexpr (SPLIT) {
         if (lane == 0) s_is[wave] = IssueStateS{};   // cur_next == cur_end: no item open
@@ -472,6 +472,6 @@
         if (wcount[wave][3]) atomicAdd(cc + kDirectSkySlot, wcount[wave][3]);
         for (uint32_t i = 0; i < kNWork; ++i) atomicAdd(cc + kWorkSlot + i, g_work[wave][i]);
 #ifdef RT_KSTATS
-        for (int i = 0; i < 8; ++i) atomicAdd(cc + 3 + i, g_kst[wave][i]);
+        for (int i = 0; i < kNKstat; ++i) atomicAdd(cc + kstat_slot(i), g_kst[wave][i]);
 #endif
     }
