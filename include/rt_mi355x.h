@@ -130,6 +130,9 @@ typedef struct rt_stats {
 /* Set (with RT_KERNEL_SPLIT): a session's item-table kernel ran, trace_paths_items<T, W, CAMQ, MEGA>
  * (rt_progressive_extend_map_async with a non-uniform map). */
 #define RT_KERNEL_ITEMS(id) (((id) >> 10) & 1u)
+/* Set: the guide-buffer kernel ran, guide_pixels<T, CAMQ, MEGA> (rt_render_guides_async); F64, WAVES, CAMQ and
+ * MEGA mean what they mean above, ROOT2, MODE, SPLIT and ITEMS are 0. */
+#define RT_KERNEL_GUIDES(id) (((id) >> 11) & 1u)
 
 /* ---- flags ---- */
 #define RT_FLAG_F32 0x1u     /* compute in fp32 (default: fp64, the reference's arithmetic) */
@@ -213,6 +216,44 @@ int rt_render_async(rt_context* ctx, const rt_camera* camera, uint32_t max_bounc
 int rt_render_split_async(rt_context* ctx, const rt_camera* camera, uint32_t max_bounces, uint32_t spp,
                           uint64_t seed, uint32_t flags, const rt_tile_range* range, void* d_rgb8,
                           void* d_linear, void* stream, uint32_t samples_per_item);
+/* ---- guide buffers: what a denoiser or an edge-aware filter needs beside a noisy preview ----
+ * Per pixel the mean first-hit albedo, normal, depth and coverage over the primary rays of the image that
+ * rt_render_async makes with the same camera, spp, seed and precision (flags).  Draws are keyed by (pixel,
+ * sample, bounce), so the guides at n samples come from exactly the primary rays of the image at n samples:
+ * their edges lie where the image's lie.  Nothing is scattered and no colour is computed.
+ * Definition, for a pixel with n = spp samples and sample s in [0, n), in the render's precision T (fp64, or
+ * fp32 under RT_FLAG_F32):
+ *   primary ray  Camera::get_ray for (col, row, s, pix = row * W + col, seed): bit for bit the ray
+ *                rt_render_async traces at bounce 0 (the same draws, the same fp32 key fold).
+ *   hit          the live path's closest hit at bounce 0: Sphere::hit_packed with quirk Q1 as the reference has
+ *                it (a ray whose near root is invalid has no hit), the later sphere wins ties, t in [0.001, inf);
+ *                then PackedHitRecords::finalize: loc = o + d t, normal = unit(loc - centre) with the packed
+ *                length, front = pk_dot(d, normal) < 0, the normal negated when not front.
+ *   per sample   albedo_s: the attenuation the render's path takes at bounce 0, i.e. the material's albedo
+ *                rounded to T for Lambertian and Metal, (1, 1, 1) for Dielectric, (1, 1, 1) on a miss;
+ *                normal_s: the finalized normal (against the ray), (0, 0, 0) on a miss;
+ *                depth_s: t (directions are unit: a distance), 0 on a miss;
+ *                coverage_s: 1 on a hit, 0 on a miss.
+ *   reduction    fixed, so that a value is a function of the samples alone, never of the launch; each channel on
+ *                its own.  Every per-sample value is converted to double; partial j (j in 0..63, starting at
+ *                +0.0) adds the samples with s % 64 == j in ascending s; the 64 partials are folded
+ *                for h in 32, 16, 8, 4, 2, 1: p[i] += p[i + h] for i < h; the output is (float)(p[0] / (double)n).
+ * Every output is float32.  The means are over all n samples, so they are premultiplied by coverage: a consumer
+ * that wants the mean over the hits divides by coverage.
+ * Outputs: device pointers, compact over the range like d_rgb8; d_albedo and d_normal [pixels][3] float,
+ * d_depth and d_coverage [pixels] float.  Any may be NULL; a value does not depend on which others were asked for.
+ * Asynchronous on `stream` under rt_render_async's cross-stream rule.  It uses the context's scene and camera
+ * tables with a render's rebuild rule, is allowed while a progressive session is open and touches neither the
+ * session's records nor its counts.
+ * flags: RT_FLAG_F32 or 0.  RT_ERR_UNSUPPORTED: RT_FLAG_ROOT2 or any RT_FLAG_MODE_*, spp > 2^20, more than
+ * 0x7FFFFFFF pixels.  RT_ERR_INVALID: unknown flag bits, ctx or camera NULL, spp == 0, all four outputs NULL, a
+ * bad range.  Never RT_ERR_RANGE: nothing is quantised.
+ * rt_context_collect after it: pixels is the pixel count, samples = ray_segments = pixels * spp, bounce_iters = 0,
+ * kernel_ms covers the kernel, RT_KERNEL_GUIDES(kernel_id) is set; the executed-work counters hold what the
+ * reused camera sweep counts. */
+int rt_render_guides_async(rt_context* ctx, const rt_camera* camera, uint32_t spp, uint64_t seed, uint32_t flags,
+                           const rt_tile_range* range, void* d_albedo, void* d_normal, void* d_depth,
+                           void* d_coverage, void* stream);
 /* The plan rt_render_split_async makes for samples_per_item = 0; host only, needs no GPU.
  * resident_waves: the waves the split kernels keep resident (CUs x 4 SIMDs x 5 waves in fp32, x 4 in fp64).
  * Returns the samples per item (a multiple of 128, or spp when the plan is one item per pixel) and the

@@ -30,13 +30,15 @@
 // Source layout (one translation unit): rt_experiments.hpp (build kinds), rt_formats.hpp (the formats host
 // layout and device code share; no HIP), rt_common.hpp (kernel arguments, scalar-load pipelines),
 // rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (replay + reduction),
-// rt_trace.hpp + rt_trace_body.hpp (the persistent kernel); and, host only, without HIP: rt_layout.hpp (the
-// scene image: every device table of a scene, build_scene_image), rt_split_plan.hpp (the sample-parallel
-// plan), rt_progressive_plan.hpp (a progressive session's record buffer and sample windows).  This file holds
-// the C ABI: the context and its device tables, the launch steps (scene_params, frame_params,
-// ensure_cam_tables, plan_grid) and the launchers (launch_plain, launch_split, launch_window; launch_items and
-// launch_classes for a session's per-pixel counts).
+// rt_trace.hpp + rt_trace_body.hpp (the persistent kernel), rt_guides.hpp (guide buffers: first hits only);
+// and, host only, without HIP: rt_layout.hpp (the scene image: every device table of a scene,
+// build_scene_image), rt_split_plan.hpp (the sample-parallel plan), rt_progressive_plan.hpp (a progressive
+// session's record buffer and sample windows).  This file holds the C ABI: the context and its device tables,
+// the launch steps (scene_params, frame_params, ensure_cam_tables, plan_grid) and the launchers (launch_plain,
+// launch_split, launch_window; launch_items and launch_classes for a session's per-pixel counts;
+// launch_guides).
 #include "rt_trace.hpp"
+#include "rt_guides.hpp"
 #include "rt_layout.hpp"
 #include "rt_split_plan.hpp"
 #include "rt_progressive_plan.hpp"
@@ -432,6 +434,12 @@ static void (*pick_items(bool mega))(IParams<T>) {
     constexpr int W = kWavesSplit<T>;
     return mega ? trace_paths_items<T, W, CAMQ, true> : trace_paths_items<T, W, CAMQ, false>;
 }
+// The guide-buffer kernel (rt_render_guides_async): guide_pixels<T, CAMQ, MEGA> (RT_KERNEL_GUIDES in the kernel id).
+constexpr uint32_t kKernelGuidesBit = 1u << 11;
+template <typename T, bool CAMQ>
+static void (*pick_guides(bool mega))(GParams<T>) {
+    return mega ? guide_pixels<T, CAMQ, true> : guide_pixels<T, CAMQ, false>;
+}
 constexpr uint64_t kScratchBudget = 24ull << 30;   // scratch (and record buffer) bytes a launch may ask for
 
 // ---- the steps of a launch ----
@@ -666,6 +674,35 @@ static int launch_plain(rt_context* c, const FrameArgs& a, hipStream_t st) {
     p.scratch = (char*)c->scratch.p;
     if ((rc = zero_claim_counters(c, st)) != RT_OK) return rc;
     hipLaunchKernelGGL(pick.fn, dim3((uint32_t)nblocks), dim3(256), 0, st, p);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// guide_pixels: the waves stride over the pixels of the range, each keeping a pixel for all its samples.  No
+// scratch, no records, no claim counter; the frame is set up as a render's of one bounce, so the camera tables
+// follow a render's rebuild rule.
+template <typename T>
+static int launch_guides(rt_context* c, const FrameArgs& a, float* albedo, float* normal, float* depth, float* coverage,
+                         hipStream_t st) {
+    KParams<T> p;
+    bool camq = false;
+    int rc = frame_setup(c, a, 1u, st, p, camq);
+    if (rc != RT_OK) return rc;
+    const bool mega = p.n_mg > 0;
+    void (*const gfn)(GParams<T>) = camq ? pick_guides<T, true>(mega) : pick_guides<T, false>(mega);
+    constexpr int W = kWavesGuide<T>;
+    const uint32_t id = 0x8000u | (sizeof(T) == 8 ? 1u : 0u) | ((uint32_t)W << 1) | (camq ? 1u << 7 : 0u) |
+                        (mega ? 1u << 8 : 0u) | kKernelGuidesBit;
+    uint64_t nblocks = 0;
+    if ((rc = plan_grid(c, (const void*)gfn, W, id, p.n_items, a.spp, nblocks, p.blk_g)) != RT_OK) return rc;
+    GParams<T> gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.k = p;
+    gp.albedo = albedo;
+    gp.normal = normal;
+    gp.depth = depth;
+    gp.coverage = coverage;
+    hipLaunchKernelGGL(gfn, dim3((uint32_t)nblocks), dim3(256), 0, st, gp);
     HIPCHK(hipGetLastError());
     return RT_OK;
 }
@@ -976,6 +1013,27 @@ extern "C" int rt_render_split_async(rt_context* c, const rt_camera* cam, uint32
                                      void* d_linear, void* stream, uint32_t samples_per_item) {
     return render_async(c, cam, max_bounces, spp, seed, flags, range, d_rgb8, d_linear, stream, "rt_render_split_async",
                         samples_per_item == 0u ? 0 : 1, samples_per_item);
+}
+
+extern "C" int rt_render_guides_async(rt_context* c, const rt_camera* cam, uint32_t spp, uint64_t seed, uint32_t flags,
+                                      const rt_tile_range* range, void* d_albedo, void* d_normal, void* d_depth,
+                                      void* d_coverage, void* stream) {
+    const std::string who = "rt_render_guides_async";
+    if (!c || !cam) return fail(RT_ERR_INVALID, who + ": NULL argument");
+    if (spp == 0) return fail(RT_ERR_INVALID, who + ": spp == 0");
+    if (!d_albedo && !d_normal && !d_depth && !d_coverage) return fail(RT_ERR_INVALID, who + ": all four outputs are NULL");
+    // the frame of a render that stops after its first hit: one bounce
+    FrameArgs a{cam, 1u, spp, seed, flags, rt_tile_range{}, nullptr, nullptr};
+    int rc = check_frame(who, cam, flags, true, "spp", spp, 1u, range, &a.rg);
+    if (rc != RT_OK) return rc;
+    const uint64_t n_pix = (uint64_t)a.rg.row_count * a.rg.col_count;
+    if (n_pix > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many pixels in one call");
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = begin_launch(c, st)) != RT_OK) return rc;
+    rc = (flags & RT_FLAG_F32) ? launch_guides<float>(c, a, (float*)d_albedo, (float*)d_normal, (float*)d_depth, (float*)d_coverage, st)
+                               : launch_guides<double>(c, a, (float*)d_albedo, (float*)d_normal, (float*)d_depth, (float*)d_coverage, st);
+    if (rc != RT_OK) return rc;
+    return end_launch(c, st, n_pix, n_pix * spp);
 }
 
 extern "C" int rt_split_plan(uint64_t n_pixels, uint32_t spp, uint32_t resident_waves, uint32_t* samples_per_item,

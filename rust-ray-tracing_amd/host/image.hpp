@@ -56,6 +56,23 @@ inline void write_png(const std::string& path, uint32_t w, uint32_t h, const uin
     if (!ok) throw std::runtime_error("short write to " + path);
 }
 
+// PFM, the exact float32 values (guide buffers): "PF" for three channels, "Pf" for one, scale -1.0 (little-endian),
+// rows bottom to top.  data: row-major from the top row, `channels` floats per pixel.
+inline void write_pfm(const std::string& path, uint32_t w, uint32_t h, uint32_t channels, const float* data) {
+    static_assert(sizeof(float) == 4, "PFM holds IEEE float32");
+    const uint16_t probe = 1;
+    if (*(const uint8_t*)&probe != 1) throw std::runtime_error("write_pfm: a big-endian host");
+    if (channels != 1 && channels != 3) throw std::runtime_error("write_pfm: 1 or 3 channels");
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) throw std::runtime_error("cannot open " + path);
+    std::fprintf(f, "%s\n%u %u\n-1.0\n", channels == 3 ? "PF" : "Pf", w, h);
+    const size_t row = (size_t)w * channels;
+    bool ok = true;
+    for (uint32_t y = h; y-- > 0 && ok;) ok = std::fwrite(data + (size_t)y * row, sizeof(float), row, f) == row;
+    std::fclose(f);
+    if (!ok) throw std::runtime_error("short write to " + path);
+}
+
 inline void save_image(const std::string& path, uint32_t w, uint32_t h, const uint8_t* rgb) {
     if (path.size() >= 4 && (path.compare(path.size() - 4, 4, ".ppm") == 0)) write_ppm(path, w, h, rgb);
     else write_png(path, w, h, rgb);

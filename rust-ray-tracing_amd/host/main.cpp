@@ -3,7 +3,7 @@
 //   rt-render [--scene scene.toml] [--width 3840] [--height 2160] [--spp 100] [--bounces 50]
 //             [--seed 0x5EED0001] [--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar]
 //             [--out output.png|.ppm] [--block-size B] [--sample-parallel] [--progressive n1,n2,...]
-//             [--adaptive TOL --spp-min N [--count-map counts.png|.ppm] [--device-plan]] [--dump-scene]
+//             [--adaptive TOL --spp-min N [--count-map counts.png|.ppm] [--device-plan]] [--guides] [--dump-scene]
 //
 // --mode picks which of the reference's renderers is reproduced (include/rt_mi355x.h): the live
 // render_vectorized2 (default), render_vectorized, or the scalar render.
@@ -20,6 +20,11 @@
 // pixels x spp.  --count-map PATH writes each pixel's count as grey RGB8, 255 * count / spp.  The live path only.
 // --device-plan (with --adaptive) keeps the estimate, the selection and the item table on the GPU
 // (rt_progressive_refine): the same lines, the same files, a few words between host and device per step.
+// --guides also writes the guide buffers a denoiser wants beside the image (rt_render_guides_async): <out stem>_albedo.pfm,
+// _normal.pfm, _depth.pfm and _coverage.pfm next to --out, the exact float32 values (PFM: "PF" three channels, "Pf"
+// one, scale -1.0, little-endian, rows bottom to top).  They are always the uniform guides at --spp, from the
+// primary rays of the image at --spp, whatever way the image itself was sampled; --out is the file the command
+// writes without --guides.  One line gives the guide pass's kernel time and sample rate.  The live path only.
 //
 // Defaults are main.rs's hard-coded values (scene.toml in the working directory, 3840x2160, 50
 // bounces, 100 spp, camera from (16,2,18.5) looking at the origin, vfov 30, focal 10, no defocus,
@@ -83,7 +88,7 @@ int main(int argc, char** argv) {
     std::string scene_path = "scene.toml", out = "output.png";
     uint32_t width = 3840, height = 2160, spp = 100, bounces = 50, flags = 0, block_size = 0;
     uint64_t seed = 0x5EED0001ull;
-    bool dump = false, sample_parallel = false;
+    bool dump = false, sample_parallel = false, guides = false;
     std::string progressive_arg, count_map;
     bool progressive = false, adaptive = false, device_plan = false;
     double tolerance = 0.0;
@@ -118,12 +123,13 @@ int main(int argc, char** argv) {
         else if (a == "--spp-min") spp_min = (uint32_t)std::stoul(next());
         else if (a == "--count-map") count_map = next();
         else if (a == "--device-plan") device_plan = true;
+        else if (a == "--guides") guides = true;
         else if (a == "--dump-scene") dump = true;
         else if (a == "-h" || a == "--help") {
             std::puts("rt-render [--scene scene.toml] [--width W] [--height H] [--spp S] [--bounces B] [--seed N] "
                       "[--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar] [--out output.png] [--block-size B] "
                       "[--sample-parallel] [--progressive n1,n2,...] [--adaptive TOL --spp-min N [--count-map PATH] "
-                      "[--device-plan]] [--dump-scene]");
+                      "[--device-plan]] [--guides] [--dump-scene]");
             return 0;
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -169,6 +175,16 @@ int main(int argc, char** argv) {
     } else if (spp_min != 0 || !count_map.empty() || device_plan) {
         std::fprintf(stderr, "--spp-min, --count-map and --device-plan go with --adaptive\n");
         return 2;
+    }
+    if (guides) {
+        auto bad = [](const std::string& why) {
+            std::fprintf(stderr, "--guides: %s\n", why.c_str());
+            return 2;
+        };
+        if (flags & RT_FLAG_ROOT2) return bad("not with --root2: the guides are the live path's first hits");
+        if (flags & (RT_FLAG_MODE_VECTORIZED | RT_FLAG_MODE_SCALAR | RT_FLAG_MODE_VECTORIZED3))
+            return bad("only with --mode vectorized2: the guides are the live path's first hits");
+        if (block_size != 0) return bad("not with --block-size: the guide pass is one launch over the whole image");
     }
     try {
         std::ifstream in(scene_path, std::ios::binary);   // main.rs:31-34
@@ -220,6 +236,19 @@ int main(int argc, char** argv) {
                              : progressive ? renderer.render_progressive(bounces, spp, scene, camera, counts, step)
                                            : renderer.render(bounces, spp, scene, camera);     // main.rs:64
         save_image(out, image.width, image.height, image.data.data());                         // main.rs:66
+        if (guides) {
+            const GpuRenderer::Guides g = renderer.render_guides(spp, scene, camera);
+            const size_t dot = out.find_last_of('.'), slash = out.find_last_of('/');
+            const bool ext = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+            const std::string stem = ext ? out.substr(0, dot) : out;
+            write_pfm(stem + "_albedo.pfm", g.width, g.height, 3, g.albedo.data());
+            write_pfm(stem + "_normal.pfm", g.width, g.height, 3, g.normal.data());
+            write_pfm(stem + "_depth.pfm", g.width, g.height, 1, g.depth.data());
+            write_pfm(stem + "_coverage.pfm", g.width, g.height, 1, g.coverage.data());
+            std::printf("Guides: %u spp -> %s_{albedo,normal,depth,coverage}.pfm, kernel %.3f ms, %.2f Msamples/s\n", spp,
+                        stem.c_str(), g.gpu.kernel_ms,
+                        g.gpu.kernel_ms > 0 ? (double)g.gpu.samples / (g.gpu.kernel_ms * 1e-3) / 1e6 : 0.0);
+        }
         if (adaptive) {
             const double full = (double)image.width * image.height * spp;
             std::printf("Adaptive: %u steps, %llu samples traced, %.1f %% of %u x %u x %u spp\n", steps,

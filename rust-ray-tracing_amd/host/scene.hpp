@@ -457,6 +457,48 @@ struct GpuRenderer : Renderer {
         return {std::move(img), stat};
     }
 
+    // Guide buffers (rt_render_guides_async): per pixel the mean first-hit albedo, normal, depth and coverage over
+    // the primary rays of render()'s image at spp samples, as exact float32 values, row-major from the top row.
+    // One launch over the whole image on a context of its own.  The live path only.
+    struct Guides {
+        uint32_t width = 0, height = 0;
+        std::vector<float> albedo, normal, depth, coverage;   // [h][w][3], [h][w][3], [h][w], [h][w]
+        rt_stats gpu{};
+    };
+    Guides render_guides(size_t spp, const Scene& scene, const Camera& camera) {
+        FlatScene flat = scene.flatten();
+        rt_scene rs = flat.view();
+        Guides g;
+        g.width = camera.image_width();
+        g.height = camera.image_height();
+        const size_t npx = (size_t)g.width * g.height;
+        struct Ctx {
+            rt_context* c = nullptr;
+            void* buf[4] = {nullptr, nullptr, nullptr, nullptr};
+            ~Ctx() {
+                for (void* b : buf) if (b) rt_device_free(c, b);
+                if (c) rt_context_destroy(c);
+            }
+        } x;
+        auto chk = [](int rc, const char* what) {
+            if (rc != RT_OK) throw Panic(std::string(what) + ": " + rt_last_error());
+        };
+        chk(rt_context_create(0, &x.c), "rt_context_create");
+        chk(rt_context_set_scene(x.c, &rs), "rt_context_set_scene");
+        std::vector<float>* out[4] = {&g.albedo, &g.normal, &g.depth, &g.coverage};
+        const size_t ch[4] = {3, 3, 1, 1};
+        for (int i = 0; i < 4; ++i) chk(rt_device_alloc(x.c, npx * ch[i] * sizeof(float), &x.buf[i]), "rt_device_alloc");
+        chk(rt_render_guides_async(x.c, &camera.c, (uint32_t)spp, seed, flags, nullptr, x.buf[0], x.buf[1], x.buf[2],
+                                   x.buf[3], nullptr),
+            "rt_render_guides_async");
+        chk(rt_context_collect(x.c, nullptr, &g.gpu), "rt_context_collect");
+        for (int i = 0; i < 4; ++i) {
+            out[i]->resize(npx * ch[i]);
+            chk(rt_memcpy_d2h(x.c, out[i]->data(), x.buf[i], npx * ch[i] * sizeof(float)), "rt_memcpy_d2h");
+        }
+        return g;
+    }
+
   private:
     void render_blocks(const rt_scene& rs, const Camera& camera, uint32_t max_bounces, uint32_t spp, RgbImage& img,
                        rt_stats& total, uint32_t B, bool print_blocks) {

@@ -6,7 +6,7 @@ lib/librt_mi355x.so; this package only binds it and mirrors the reference's host
 from . import abi
 from .abi import load_library, RtError
 from .scene import Camera, Dielectric, FlatScene, Lambertian, Metal, Scene, Sphere, MAIN_CAMERA, camera_new_py
-from .renderer import GpuRenderer, ProgressiveSession, RenderStat, Renderer
+from .renderer import GpuRenderer, Guides, ProgressiveSession, RenderStat, Renderer
 from . import scenes
 from . import parallel
 from . import toml_scene
@@ -14,5 +14,5 @@ from .toml_scene import Panic, load_scene, scene_from_toml
 
 __all__ = [
     "abi", "load_library", "RtError", "Camera", "Dielectric", "FlatScene", "Lambertian", "Metal", "Scene",
-    "Sphere", "MAIN_CAMERA", "camera_new_py", "GpuRenderer", "ProgressiveSession", "RenderStat", "Renderer", "scenes", "parallel", "toml_scene", "Panic", "load_scene", "scene_from_toml",
+    "Sphere", "MAIN_CAMERA", "camera_new_py", "GpuRenderer", "Guides", "ProgressiveSession", "RenderStat", "Renderer", "scenes", "parallel", "toml_scene", "Panic", "load_scene", "scene_from_toml",
 ]

@@ -86,13 +86,19 @@ def RT_KERNEL_ITEMS(kernel_id):
     return (kernel_id >> 10) & 1
 
 
+def RT_KERNEL_GUIDES(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_GUIDES: the guide-buffer kernel ran (rt_render_guides_async)."""
+    return (kernel_id >> 11) & 1
+
+
 def kernel_info(kernel_id):
     """rt_stats.kernel_id decoded (include/rt_mi355x.h RT_KERNEL_*): the trace_paths instantiation that ran."""
     if kernel_id == 0:
         return None
     return {"T": "double" if kernel_id & 1 else "float", "W": (kernel_id >> 1) & 7, "root2": bool((kernel_id >> 4) & 1),
             "mode": (kernel_id >> 5) & 3, "camq": bool((kernel_id >> 7) & 1), "mega": bool((kernel_id >> 8) & 1),
-            "split": bool(RT_KERNEL_SPLIT(kernel_id)), "items": bool(RT_KERNEL_ITEMS(kernel_id))}
+            "split": bool(RT_KERNEL_SPLIT(kernel_id)), "items": bool(RT_KERNEL_ITEMS(kernel_id)),
+            "guides": bool(RT_KERNEL_GUIDES(kernel_id))}
 
 
 def kernel_name(kernel_id):
@@ -101,6 +107,8 @@ def kernel_name(kernel_id):
     if k is None:
         return None
     b = lambda v: "true" if v else "false"
+    if k["guides"]:   # guide_pixels<T,CAMQ,MEGA>
+        return f"guide_pixels<{k['T']},{b(k['camq'])},{b(k['mega'])}>"
     if k["items"]:   # trace_paths_items<T,W,CAMQ,MEGA> (finish_window_list<T> follows it)
         return f"trace_paths_items<{k['T']},{k['W']},{b(k['camq'])},{b(k['mega'])}>"
     if k["split"]:   # trace_paths_split<T,W,CAMQ,MEGA> (finish_records<T> follows it)
@@ -136,6 +144,7 @@ EXPORTED = [
     "rt_progressive_bytes", "rt_progressive_begin", "rt_progressive_extend_async", "rt_progressive_end",
     "rt_progressive_extend_map_async", "rt_progressive_snapshot_map_async", "rt_progressive_counts",
     "rt_progressive_error_async", "rt_progressive_map_plan", "rt_progressive_refine", "rt_progressive_refine_items",
+    "rt_render_guides_async",
 ]
 
 _lib = None
@@ -143,7 +152,7 @@ _lib = None
 # The sources the Makefile hashes into rt_version() ("src=<hash>"), in its order (SRC, then HDR).
 KERNEL_SOURCES = ["rt_kernel.hip", "rt_experiments.hpp", "rt_formats.hpp", "rt_common.hpp", "rt_sweep.hpp",
                   "rt_camera.hpp", "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp",
-                  "rt_progressive_plan.hpp"]
+                  "rt_progressive_plan.hpp", "rt_guides.hpp"]
 SOURCE_FILES = [os.path.join(PKG_DIR, "csrc", f) for f in KERNEL_SOURCES] + \
                [os.path.join(os.path.dirname(PKG_DIR), "include", "rt_mi355x.h")]
 
@@ -196,6 +205,7 @@ def load_library(path=None):
     lib.rt_context_set_scene.argtypes = [vp, P(RtScene)]
     lib.rt_render_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp]
     lib.rt_render_split_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp, u32]
+    lib.rt_render_guides_async.argtypes = [vp, P(RtCamera), u32, u64, u32, P(RtTileRange), vp, vp, vp, vp, vp]
     lib.rt_split_plan.argtypes = [u64, u32, u32, P(u32), P(u64)]
     lib.rt_progressive_bytes.argtypes = [u64, u32, u32, u32, P(u64)]
     lib.rt_progressive_begin.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), u64]

@@ -9,6 +9,7 @@ RenderStat).  Where the reference panics (Color::to_u8_array's `<= 2.0` assert,
 color.rs:55-57; unknown material, materials.rs:31; spp == 0 -> 0/0) this raises RtError.
 There is no CPU fallback: the HIP library must be built and a GPU present.
 """
+import collections
 import ctypes
 import time
 
@@ -80,6 +81,11 @@ def check_schedule(schedule):
 
 
 ADAPTIVE_PLANS = ("host", "device")
+
+# Guide buffers (rt_render_guides_async), in the C ABI's argument order, and their channels per pixel.
+GUIDE_NAMES = ("albedo", "normal", "depth", "coverage")
+GUIDE_CHANNELS = {"albedo": 3, "normal": 3, "depth": 1, "coverage": 1}
+Guides = collections.namedtuple("Guides", GUIDE_NAMES)
 
 
 def check_adaptive(spp_min, spp_max, tolerance, plan="host"):
@@ -377,6 +383,65 @@ class GpuRenderer(Renderer):
             raise abi.RtError(rc, "a pixel channel exceeded 2.0 (reference: Color::to_u8_array panics)")
         img = rgb.reshape(cam.image_height, cam.image_width, 3)
         return img, RenderStat(dt, cam.image_width * cam.image_height, st.kernel_ms, st.samples, st.ray_segments)
+
+    def _check_guides(self, want=GUIDE_NAMES):
+        """The guide calls' arguments checked before any GPU call: the live path only, known output names."""
+        if self.flags & ~abi.RT_FLAG_F32:
+            raise ValueError("guide buffers are the live path's first hits: mode 'vectorized2' without root2 only")
+        want = tuple(want)
+        for name in want:
+            if name not in GUIDE_NAMES:
+                raise ValueError(f"unknown guide buffer {name!r} (one of {list(GUIDE_NAMES)})")
+        if not want:
+            raise ValueError("no guide buffer asked for")
+        return want
+
+    def guides_flat(self, spp, flat, cam, tile_range=None, want=GUIDE_NAMES):
+        """rt_render_guides_async with a FlatScene / RtCamera: per pixel the mean first-hit albedo, normal, depth and
+        coverage over the primary rays of render_flat's image at `spp` (the renderer's seed and precision; the
+        definition is in include/rt_mi355x.h).  Returns ({name: float32 array, flat over the range}, RtStats, rc):
+        albedo and normal [n, 3], depth and coverage [n].  want: the buffers to compute the outputs of (a value
+        does not depend on which others are asked for)."""
+        want = self._check_guides(want)
+        lib = self.lib
+        if self._scene_flat is not flat:
+            self.set_scene(flat)
+        tr = tile_range if tile_range is not None else abi.RtTileRange(0, 1, cam.image_height, 0, cam.image_width)
+        npx = tr.row_count * tr.col_count
+        dev = {name: ctypes.c_void_p() for name in want}
+        out = {}
+        try:
+            for name in want:
+                abi.check(lib, lib.rt_device_alloc(self.ctx, npx * GUIDE_CHANNELS[name] * 4, ctypes.byref(dev[name])))
+            abi.check(lib, lib.rt_render_guides_async(self.ctx, ctypes.byref(cam), spp, self.seed, self.flags,
+                                                      ctypes.byref(tr), *[dev.get(name) for name in GUIDE_NAMES], None))
+            st = abi.RtStats()
+            rc = abi.check(lib, lib.rt_context_collect(self.ctx, None, ctypes.byref(st)))
+            for name in want:
+                ch = GUIDE_CHANNELS[name]
+                a = np.empty((npx, ch) if ch > 1 else (npx,), dtype=np.float32)
+                abi.check(lib, lib.rt_memcpy_d2h(self.ctx, a.ctypes.data, dev[name], npx * ch * 4))
+                out[name] = a
+        finally:
+            for d in dev.values():
+                if d:
+                    lib.rt_device_free(self.ctx, d)
+        return out, st, rc
+
+    def guides(self, spp, scene, camera):
+        """The guide buffers of render()'s image at `spp` samples: (Guides(albedo (H, W, 3), normal (H, W, 3),
+        depth (H, W), coverage (H, W)) of float32, RenderStat).  The means are over all samples of a pixel, so
+        they are premultiplied by coverage."""
+        self._check_guides()   # before any GPU call
+        t0 = time.perf_counter()
+        flat = scene.flatten() if hasattr(scene, "flatten") else scene
+        cam = camera.abi if hasattr(camera, "abi") else camera
+        out, st, _ = self.guides_flat(spp, flat, cam)
+        dt = time.perf_counter() - t0
+        h, w = cam.image_height, cam.image_width
+        g = Guides(out["albedo"].reshape(h, w, 3), out["normal"].reshape(h, w, 3), out["depth"].reshape(h, w),
+                   out["coverage"].reshape(h, w))
+        return g, RenderStat(dt, w * h, st.kernel_ms, st.samples, st.ray_segments)
 
     def begin_progressive(self, max_bounces, spp_capacity, scene, camera, tile_range=None, max_bytes=0):
         """Open a ProgressiveSession (rt_progressive_begin) for up to spp_capacity samples per pixel.  The live
