@@ -1,5 +1,6 @@
 """Degenerate scenes shared by tests/test_edge_scenes.py (CPU: each scene does on the oracle what it is
-meant to) and tests/test_gpu_scene_edges.py (GPU: the HIP kernels against the oracle on them).
+meant to) and tests/test_gpu_scene_edges.py (GPU: the HIP kernels against the oracle on them), and by
+tests/test_guide_edges.py and tests/test_gpu_guide_edges.py (the guide kernel against its restatement on them).
 
 Plain module: no GPU, no fixtures.  Every builder is deterministic (fixed numpy seeds) and returns
 (FlatScene, RtCamera).  The cameras of the scenes the independent restatement also renders are module
@@ -55,18 +56,30 @@ def twins_mega(w=8, h=5, swap=False):
 STACK_CAMERA = dict(rt.MAIN_CAMERA, center=(2.5, 1.5, 3.0), look_at=(0.0, 1.0, 0.0))
 
 
-def stack(w=16, h=9, reverse=False):
-    """Ground plus 40 identical spheres (centre (0, 1, 0), radius 1) with 40 distinct Lambertian albedos; the
-    camera is 4 units away.  reverse: the 40 materials in the opposite order."""
+def stack(w=16, h=9, reverse=False, n=40):
+    """Ground plus n (40) identical spheres (centre (0, 1, 0), radius 1) with n distinct Lambertian albedos; the
+    camera is 4 units away.  reverse: the n materials in the opposite order."""
     rng = np.random.default_rng(41)
-    albedo = rng.uniform(0.05, 0.95, (40, 3))
+    albedo = rng.uniform(0.05, 0.95, (n, 3))
     mats = [rt.Lambertian((0.5, 0.5, 0.5))] + [rt.Lambertian(tuple(a)) for a in albedo]
-    order = np.arange(1, 41)
+    order = np.arange(1, n + 1)
     if reverse:
         order = order[::-1]
-    center = np.array([[0.0, -1000.0, 0.0]] + [[0.0, 1.0, 0.0]] * 40)
-    radius = np.array([1000.0] + [1.0] * 40)
+    center = np.array([[0.0, -1000.0, 0.0]] + [[0.0, 1.0, 0.0]] * n)
+    radius = np.array([1000.0] + [1.0] * n)
     flat = rt.FlatScene(center, radius, np.concatenate([[0], order]).astype(np.uint32), mats)
+    return flat, camera(w, h, **STACK_CAMERA)
+
+
+COVER_ALBEDO = (0.3, 0.55, 0.7)
+COVER_CENTER, COVER_RADIUS = (0.0, 1.0, 0.0), 2.0
+
+
+def cover(w=3, h=3):
+    """One Lambertian sphere (radius 2 at (0, 1, 0)) and no ground under the stack's camera, which looks at its
+    centre from outside: the middle pixel of a small odd frame has its whole footprint on the sphere."""
+    flat = rt.FlatScene(np.array([COVER_CENTER]), np.array([COVER_RADIUS]), np.zeros(1, np.uint32),
+                        [rt.Lambertian(COVER_ALBEDO)])
     return flat, camera(w, h, **STACK_CAMERA)
 
 

@@ -11,7 +11,7 @@ import pytest
 import rt_mi355x as rt
 from rt_mi355x import abi
 from rt_mi355x import renderer as rmod
-from test_gpu_guides import fold   # the GPU tests' restatement (importing it needs no GPU)
+from guide_restatement import fold   # the GPU tests' restatement
 
 
 def test_symbol_is_exported_and_declared():
