@@ -118,6 +118,15 @@ void oracle_get_ray_f64(const or_camera* cam, uint32_t col, uint32_t row, uint32
 ORACLE_PROBE_DECLS(double, f64)
 ORACLE_PROBE_DECLS(float, f32)
 
+/* The nearest hit of n single rays, brute force over every sphere in scene order (the per-ray reference of
+ * tests/test_gpu_cull_probe.py).  o, d: component-major.  mode 0: hit_packed + PackedHitRecords::update (Q1; a
+ * later sphere wins a tie), 1: the same under OR_FLAG_ROOT2, 2: Sphere::hit + Scene::hit (the first minimum wins).
+ * idx_out: scene index or -1; t_out: the root or +inf.  Returns 0, or 1 on bad arguments. */
+int oracle_nearest_hit_f64(const or_scene* sc, uint32_t mode, size_t n, const double* o, const double* d,
+                           int32_t* idx_out, double* t_out);
+int oracle_nearest_hit_f32(const or_scene* sc, uint32_t mode, size_t n, const float* o, const float* d,
+                           int32_t* idx_out, float* t_out);
+
 /* The reference-shaped CPU baseline (packed_avx2.h): the same results as oracle_render_f64, computed
  * the way the reference runs them (4-lane f64 AVX2 packets, 128x128 tiles through a shared queue).
  * rgb_out / lin_out are full-frame (W*H*3); only the listed tiles (row-major tile grid; NULL = all)

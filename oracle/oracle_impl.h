@@ -805,3 +805,57 @@ int SFX(oracle_render)(const or_scene* sc, const or_camera* cam, uint32_t max_bo
     if (segments) *segments = J.segs;
     return J.panic ? 3 : 0;
 }
+
+/* The nearest hit of n single rays against every sphere of the scene, in scene order (the per-ray reference of
+ * tests/test_gpu_cull_probe.py).  o, d: component-major origins and directions.  mode 0: hit_packed folded as
+ * PackedHitRecords::update does (Q1: root1 only; a later sphere wins a tie); 1: the same with OR_FLAG_ROOT2;
+ * 2: scene_hit_scalar (the first minimum wins).  idx_out: the scene index, -1 for no hit; t_out: its root, +inf for
+ * no hit.  No cull, no layout: hit_packed takes four rays a call, with the sphere's index in the material's place. */
+int SFX(oracle_nearest_hit)(const or_scene* sc, uint32_t mode, size_t n, const REAL* o, const REAL* d, int32_t* idx_out,
+                            REAL* t_out) {
+    if (!sc || mode > 2u || (n && (!o || !d || !idx_out || !t_out))) return 1;
+    if (sc->n_spheres && (!sc->center || !sc->radius)) return 1;
+    SFX(scene_r) S;
+    S.n = sc->n_spheres;
+    S.cx = (REAL*)malloc(sizeof(REAL) * (4 * (size_t)S.n + 4));
+    if (!S.cx) return 1;
+    S.cy = S.cx + S.n + 1; S.cz = S.cy + S.n + 1; S.r = S.cz + S.n + 1;
+    S.mat = NULL; S.mats = NULL;
+    for (uint32_t i = 0; i < S.n; ++i) {
+        S.cx[i] = (REAL)sc->center[3 * i]; S.cy[i] = (REAL)sc->center[3 * i + 1];
+        S.cz[i] = (REAL)sc->center[3 * i + 2]; S.r[i] = (REAL)sc->radius[i];
+    }
+    if (mode == 2u) {
+        for (size_t k = 0; k < n; ++k) {
+            REAL t;
+            uint32_t i = 0;
+            const int hit = SFX(scene_hit_scalar)(&S, SFX(mk)(o[k], o[n + k], o[2 * n + k]),
+                                                  SFX(mk)(d[k], d[n + k], d[2 * n + k]), &t, &i);
+            idx_out[k] = hit ? (int32_t)i : -1;
+            t_out[k] = hit ? t : (REAL)INFINITY;
+        }
+    } else {
+        const uint32_t flags = mode == 1u ? OR_FLAG_ROOT2 : 0u;
+        for (size_t k0 = 0; k0 < n; k0 += 4) {
+            SFX(prays) R;
+            SFX(phit) H;
+            memset(&R, 0, sizeof(R));
+            memset(&H, 0, sizeof(H));
+            for (int l = 0; l < 4; ++l) {
+                const size_t k = k0 + (size_t)l;
+                H.t[l] = (REAL)INFINITY;                      /* PackedHitRecords::default, objects.rs:124-133 */
+                if (k >= n) continue;                         /* a lane past the end stays disabled */
+                R.ox[l] = o[k]; R.oy[l] = o[n + k]; R.oz[l] = o[2 * n + k];
+                R.dx[l] = d[k]; R.dy[l] = d[n + k]; R.dz[l] = d[2 * n + k];
+                R.en[l] = 1;
+            }
+            for (uint32_t i = 0; i < S.n; ++i) SFX(hit_packed)(&R, S.cx[i], S.cy[i], S.cz[i], S.r[i], i, &H, flags);
+            for (int l = 0; l < 4 && k0 + (size_t)l < n; ++l) {
+                idx_out[k0 + l] = H.hit[l] ? (int32_t)H.mat[l] : -1;
+                t_out[k0 + l] = H.t[l];
+            }
+        }
+    }
+    free(S.cx);
+    return 0;
+}

@@ -9,6 +9,8 @@
 // Every entry point takes host pointers, allocates, copies, launches, synchronises, copies back, frees,
 // and returns the HIP error as an int (-1: n is no multiple of 256).
 #include "rt_sweep.hpp"
+#include "rt_camera.hpp"
+#include "rt_layout.hpp"
 
 using namespace rt;
 
@@ -120,6 +122,146 @@ __global__ void k_sqrt_sweep(uint32_t start, uint32_t iters, int mode, unsigned 
             if (slot < kFirst) first[slot] = bits;
         }
     }
+}
+
+// ---- the ray probe: the product's sweeps on the caller's rays ----
+// nearest_hit and camera_sweep read their tables through cold_args<T>(), the start of the kernarg segment, so the
+// probe kernels take KParams<T> by value as their first argument, as the product's kernels do.  Lane i holds ray i
+// and writes idx[i] / t[i] only when active[i] is set: an inactive lane's outputs stay as the caller left them.
+// General probe: inactive lanes do not enter nearest_hit (its ballots and box masks see the active lanes only).
+// Camera probe: the whole wave calls camera_sweep with v = active (a wave without any active lane is skipped:
+// camera_sweep takes its cone's axis from the first valid lane).
+template <typename T, bool ROOT2, bool SC, bool MEGA>
+__global__ void __launch_bounds__(kBlock) k_probe_general(KParams<T> p, const T* o, const T* d, const uint8_t* active,
+                                                          int32_t* idx, T* t, size_t n) {
+    const size_t i = gid();
+    if (active[i]) {
+        const V3<T> ro = ld3(o, n, i), rd = ld3(d, n, i);
+        T th;
+        const int h = nearest_hit<T, ROOT2, SC, false, MEGA>(p, ro, rd, th);
+        idx[i] = h;
+        t[i] = th;
+    }
+}
+template <typename T, bool ROOT2, bool SC, bool MEGA>
+__global__ void __launch_bounds__(kBlock) k_probe_camera(KParams<T> p, const T* d, const uint8_t* active, int32_t* idx,
+                                                         T* t, size_t n) {
+    const size_t i = gid();
+    const bool v = active[i] != 0;
+    if (__ballot(v) == 0ull) return;   // wave-uniform
+    const V3<T> rd = ld3(d, n, i);
+    T th;
+    const int h = camera_sweep<T, ROOT2, SC, MEGA>(v, rd, th);
+    if (v) {
+        idx[i] = h;
+        t[i] = th;
+    }
+}
+
+// The scene half of KParams<T> over the image's tables, uploaded through dv (rt_kernel.hip's upload_scene and
+// scene_params restated; a table the scene does not have stays unread).  The frame half stays zero.
+template <typename T> KParams<T> probe_params(Dev& dv, const SceneImage& im, bool filter_off) {
+    const SceneTables<T>& t = im.tables<T>();
+    const SceneCounts& n = im.n;
+    KParams<T> p;
+    memset(&p, 0, sizeof(p));
+    auto up = [&](const auto& v) { return dv.in(v.data(), v.size()); };
+    p.sph = up(t.sph);
+    p.cen = up(t.cen);
+    p.n_groups = t.k.n_groups;
+    p.fsph = up(t.fsph);
+    p.n_fgroups = n.n_fgroups;
+    p.rsph = up(t.rsph);
+    p.rfsph = up(t.rfsph);
+    p.ftop = up(t.top);
+    p.fsup = up(t.sup);
+    p.rflat = up(t.rflat);
+    p.n_mg = n.n_mg;
+    p.lfsph = up(t.lfs);
+    p.lclb = up(t.lbx[0]);
+    p.lsup = up(t.lbx[1]);
+    p.lmeg = up(t.lbx[2]);
+    p.lgig = up(t.lbx[3]);
+    p.n_gg = n.n_gg;
+    p.mtiers = up(im.mtiers);
+    for (int a = 0; a < 3; ++a) { p.mt_lo[a] = n.mt_lo[a]; p.mt_n[a] = n.mt_n[a]; }
+    p.mt_inv = n.mt_inv;
+    p.l_r2max = t.k.l_r2max;
+    p.l_hir2 = t.k.l_hir2;
+    p.l_isr = t.k.l_isr;
+    p.ridx = up(im.ridx);
+    p.n_top = n.n_top;
+    p.n_xg = n.n_xg;
+    p.n_xs = n.n_xs;
+    p.f_cmax = filter_off ? std::numeric_limits<float>::infinity() : t.k.f_cmax;   // RT_FILTER_OFF (frame_setup)
+    p.f_r2max = t.k.f_r2max;
+    p.f_r2min = t.k.f_r2min;
+    p.f_ir2 = t.k.f_ir2;
+    p.f_hir2 = t.k.f_hir2;
+    p.f_isr = t.k.f_isr;
+    p.mats = up(t.mats);
+    p.n_spheres = n.n_spheres;
+    return p;
+}
+
+// The camera tables of centre c (rt_kernel.hip's ensure_cam_tables restated): build_cam_table, the product's own.
+template <typename T> void probe_cam_tables(Dev& dv, const SceneImage& im, KParams<T>& p, const T* c, bool scalar,
+                                            bool filter_off) {
+    const SceneTables<T>& t = im.tables<T>();
+    const SceneCounts& n = im.n;
+    T* cam = dv.out<T>(t.cam_bytes.cam / sizeof(T));
+    float* camf = dv.out<float>(t.cam_bytes.camf / sizeof(float));
+    T* camx = dv.out<T>(t.cam_bytes.camx / sizeof(T));
+    float* cull = dv.out<float>(t.cam_bytes.cull / sizeof(float));
+    float* cullc = dv.out<float>(t.cam_bytes.cullc / sizeof(float));
+    const double* clus = dv.in(t.clus.data(), t.clus.size());
+    for (int a = 0; a < 3; ++a) p.center[a] = c[a];
+    p.camsph = cam; p.camf = camf; p.camx = camx; p.cull = cull; p.cullc = cullc;
+    p.n_clp = n.n_clp;
+    p.n_supc = n.n_supc;
+    const uint32_t n_slots = (p.n_groups + 1) * kGroup<T>, n_fslots = (p.n_fgroups + 1) * 4;
+    const uint32_t n_thr = std::max(std::max(std::max(n_slots, n_fslots), n.n_cull),
+                                    std::max(n.n_cslots, n.n_clp + n.n_supc));
+    if (!dv.ok()) return;
+    auto build = scalar ? build_cam_table<T, true> : build_cam_table<T, false>;
+    hipLaunchKernelGGL(build, dim3((n_thr + 255) / 256), dim3(256), 0, 0, p.sph, cam, n_slots, camf, n_fslots, c[0], c[1],
+                       c[2], (uint32_t)filter_off, camx, cull, n.n_cull, n.n_spheres, p.ridx, n.n_cslots, clus, cullc,
+                       n.n_clp + n.n_supc);
+    dv.sync();
+}
+
+// mode 0: the live path <T, false, false>, 1: root2 <T, true, false>, 2: scalar <T, false, true>; MEGA as the
+// launchers pick it (n_mg > 0).  centre == nullptr: the general probe.
+template <typename T>
+int probe(const rt_scene* s, int mode, int filter_off, const T* centre, const T* o, const T* d, const uint8_t* active,
+          int32_t* idx, T* t, size_t n) {
+    if (!s || mode < 0 || mode > 2 || n % kBlock != 0 || n > (1u << 24)) return -1;
+    const SceneImage im = build_scene_image(s);
+    Dev dv;
+    KParams<T> p = probe_params<T>(dv, im, filter_off != 0);
+    if (centre) probe_cam_tables<T>(dv, im, p, centre, mode == 2, filter_off != 0);
+    const T* dor = centre ? nullptr : dv.in(o, 3 * n);
+    const T* dd = dv.in(d, 3 * n);
+    const uint8_t* da = dv.in(active, n);
+    int32_t* di = dv.in(idx, n);
+    T* dt = dv.in(t, n);
+    if (dv.ok() && n) {
+        const dim3 g((unsigned)(n / kBlock)), b(kBlock);
+        const bool mega = im.n.n_mg > 0;
+#define PROBE_LAUNCH(R2, SC, MG)                                                                            \
+    do {                                                                                                    \
+        if (centre) hipLaunchKernelGGL((k_probe_camera<T, R2, SC, MG>), g, b, 0, 0, p, dd, da, di, dt, n);  \
+        else hipLaunchKernelGGL((k_probe_general<T, R2, SC, MG>), g, b, 0, 0, p, dor, dd, da, di, dt, n);   \
+    } while (0)
+        if (mode == 0) { if (mega) PROBE_LAUNCH(false, false, true); else PROBE_LAUNCH(false, false, false); }
+        else if (mode == 1) { if (mega) PROBE_LAUNCH(true, false, true); else PROBE_LAUNCH(true, false, false); }
+        else { if (mega) PROBE_LAUNCH(false, true, true); else PROBE_LAUNCH(false, true, false); }
+#undef PROBE_LAUNCH
+        dv.sync();
+    }
+    dv.back(idx, di, n);
+    dv.back(t, dt, n);
+    return (int)dv.err;
 }
 
 template <typename F> int run(size_t n, F&& body) {
@@ -240,6 +382,36 @@ int du_sqrt_sweep_f32(uint32_t start, uint64_t count, int mode, uint64_t* mismat
     d.back(first, df, kFirst);
     *mismatches = zero;
     return (int)d.err;
+}
+
+// The ray probe (above).  o, d: n rays, component-major; active: one byte per lane; idx, t: in and out (a lane that
+// is not active keeps the caller's values); idx -1 and t +inf: no hit.  The camera probe's rays all start at centre.
+int du_probe_general_f32(const rt_scene* s, int mode, int filter_off, const float* o, const float* d,
+                         const uint8_t* active, int32_t* idx, float* t, size_t n) {
+    return o ? probe<float>(s, mode, filter_off, nullptr, o, d, active, idx, t, n) : -1;
+}
+int du_probe_general_f64(const rt_scene* s, int mode, int filter_off, const double* o, const double* d,
+                         const uint8_t* active, int32_t* idx, double* t, size_t n) {
+    return o ? probe<double>(s, mode, filter_off, nullptr, o, d, active, idx, t, n) : -1;
+}
+int du_probe_camera_f32(const rt_scene* s, int mode, int filter_off, const float* centre, const float* d,
+                        const uint8_t* active, int32_t* idx, float* t, size_t n) {
+    return centre ? probe<float>(s, mode, filter_off, centre, nullptr, d, active, idx, t, n) : -1;
+}
+int du_probe_camera_f64(const rt_scene* s, int mode, int filter_off, const double* centre, const double* d,
+                        const uint8_t* active, int32_t* idx, double* t, size_t n) {
+    return centre ? probe<double>(s, mode, filter_off, centre, nullptr, d, active, idx, t, n) : -1;
+}
+// What build_scene_image makes of the scene, for the case generators (host only, no GPU): counts[8] = {n_xg, n_xs,
+// n_top, n_mg, n_gg, n_supc, n_cslots, 0}, and the first min(cap, n_cslots) words of the slot -> scene index table
+// (0xFFFFFFFF: a dummy slot; the always-exact slots first, then cluster k at 4 n_xg + 16 k).
+int du_scene_layout(const rt_scene* s, uint32_t* counts, uint32_t* ridx, size_t cap) {
+    if (!s || !counts) return -1;
+    const SceneImage im = build_scene_image(s);
+    const uint32_t c[8] = {im.n.n_xg, im.n.n_xs, im.n.n_top, im.n.n_mg, im.n.n_gg, im.n.n_supc, im.n.n_cslots, 0u};
+    memcpy(counts, c, sizeof(c));
+    for (size_t i = 0; ridx && i < cap && i < im.ridx.size(); ++i) ridx[i] = im.ridx[i];
+    return 0;
 }
 
 }  // extern "C"

@@ -38,6 +38,10 @@ def load_devunit():
                            ("hit", [vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, sz])):
             fn = getattr(lib, f"du_{name}_{sfx}")
             fn.argtypes, fn.restype = args, ctypes.c_int
+        for name, third in (("probe_general", vp), ("probe_camera", vp)):
+            fn = getattr(lib, f"du_{name}_{sfx}")
+            fn.argtypes, fn.restype = [vp, ctypes.c_int, ctypes.c_int, third, vp, vp, vp, vp, sz], ctypes.c_int
+    lib.du_scene_layout.argtypes, lib.du_scene_layout.restype = [vp, vp, vp, sz], ctypes.c_int
     lib.du_philox4x32_10.argtypes = lib.du_philox2x32_10.argtypes = [vp, vp, vp, sz]
     lib.du_fold_key_f32.argtypes, lib.du_fold_key_f32.restype = [u64], u32
     lib.du_sqrt_sweep_f32.argtypes = [u32, u64, ctypes.c_int, ctypes.POINTER(u64), vp]
@@ -189,3 +193,52 @@ def sqrt_sweep_f32(start, count, mode):
     if rc != 0:
         raise RuntimeError(f"du_sqrt_sweep_f32: HIP error {rc}")
     return mis.value, first[:min(mis.value, 16)]
+
+
+# ---- the ray probe: the product's sweeps on chosen rays (tests/test_gpu_cull_probe.py) ----
+PROBE_MODES = {"packed": 0, "root2": 1, "scalar": 2}
+IDX_UNTOUCHED = -7          # what an inactive lane's outputs hold before and after a probe
+T_UNTOUCHED = -12345.0
+
+
+def scene_layout(flat):
+    """build_scene_image's counts and slot -> scene index table of a FlatScene (host only: no GPU).
+    Returns (dict of n_xg, n_xs, n_top, n_mg, n_gg, n_supc; ridx [4 n_xg + 16 clusters] uint32, 0xFFFFFFFF: dummy)."""
+    lib = load_devunit()
+    counts = np.zeros(8, np.uint32)
+    rc = lib.du_scene_layout(ctypes.addressof(flat.abi), _p(counts), None, 0)
+    assert rc == 0, rc
+    ridx = np.zeros(int(counts[6]), np.uint32)
+    rc = lib.du_scene_layout(ctypes.addressof(flat.abi), _p(counts), _p(ridx), ridx.size)
+    assert rc == 0, rc
+    names = ("n_xg", "n_xs", "n_top", "n_mg", "n_gg", "n_supc")
+    return {k: int(v) for k, v in zip(names, counts)}, ridx[:4 * int(counts[0]) + 64 * int(counts[2])]
+
+
+def _probe(name, flat, mode, filter_off, first, d, active):
+    d = np.ascontiguousarray(d)
+    n = d.shape[1]
+    assert n % BLOCK == 0 and d.shape == (3, n) and first.dtype == d.dtype
+    active = np.ascontiguousarray(active, np.uint8)
+    assert active.shape == (n,)
+    idx = np.full(n, IDX_UNTOUCHED, np.int32)
+    t = np.full(n, T_UNTOUCHED, d.dtype)
+    _call(name, d.dtype, ctypes.addressof(flat.abi), PROBE_MODES[mode], int(bool(filter_off)), _p(first), _p(d),
+          _p(active), _p(idx), _p(t), n)
+    return idx, t
+
+
+def probe_general(flat, mode, o, d, active, filter_off=False):
+    """nearest_hit<T, ROOT2, SCALAR, false, MEGA> for the active lanes of n rays (o, d: [3, n], n a multiple of 256;
+    lane i of the launch holds ray i).  Returns (idx [n] int32, t [n]); -1 / +inf: no hit; inactive lanes hold
+    IDX_UNTOUCHED / T_UNTOUCHED."""
+    o = np.ascontiguousarray(o)
+    assert o.shape == d.shape
+    return _probe("probe_general", flat, mode, filter_off, o, d, active)
+
+
+def probe_camera(flat, mode, centre, d, active, filter_off=False):
+    """camera_sweep<T, ROOT2, SCALAR, MEGA>(active, d) per wave, over build_cam_table's tables for `centre` [3]."""
+    centre = np.ascontiguousarray(centre, d.dtype)
+    assert centre.shape == (3,)
+    return _probe("probe_camera", flat, mode, filter_off, centre, d, active)

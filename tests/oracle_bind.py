@@ -52,6 +52,9 @@ def load_oracle(path=None):
         getattr(lib, f"oracle_draw_{sfx}_n").argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, vp, sz]
         for name in ("sincos2pi", "unit_vec", "unit", "refract", "q8", "draw"):
             getattr(lib, f"oracle_{name}_{sfx}_n").restype = None
+    for sfx in ("f64", "f32"):
+        fn = getattr(lib, f"oracle_nearest_hit_{sfx}")
+        fn.argtypes, fn.restype = [vp, u32, sz, vp, vp, vp, vp], ctypes.c_int
     lib.oracle_fmix32.argtypes = [u32]
     lib.oracle_fmix32.restype = u32
     _libs[path] = lib
@@ -114,6 +117,25 @@ def oracle_draw(dtype, sid, pix, k, stream, seed):
                                                             seed & 0xFFFFFFFF, seed >> 32, r.ctypes.data, ua.ctypes.data,
                                                             ub.ctypes.data, n)
     return r, ua, ub
+
+
+NEAREST_MODES = {"packed": 0, "root2": 1, "scalar": 2}
+
+
+def oracle_nearest_hit(flat, mode, o, d):
+    """The nearest hit of each ray (o, d: [3, n], float32 or float64 picks the build), brute force over every sphere
+    of flat in scene order.  mode: "packed" (hit_packed + update, Q1), "root2" or "scalar".
+    Returns (idx [n] int32, -1 for no hit; t [n], +inf for no hit)."""
+    o = _c(o, o.dtype)
+    d = _c(d, o.dtype)
+    n = o.shape[1]
+    assert o.shape == d.shape == (3, n)
+    idx, t = np.empty(n, np.int32), np.empty(n, o.dtype)
+    rc = getattr(load_oracle(), f"oracle_nearest_hit_{_sfx(o.dtype)}")(ctypes.addressof(flat.abi), NEAREST_MODES[mode], n,
+                                                                       o.ctypes.data, d.ctypes.data, idx.ctypes.data,
+                                                                       t.ctypes.data)
+    assert rc == 0, rc
+    return idx, t
 
 
 def oracle_render(flat, cam, max_bounces, spp, seed, flags=0, pixels=None, precision="f64", threads=None,

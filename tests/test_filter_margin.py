@@ -8,6 +8,11 @@ the reference computes disc >= 0, the filter must pass.  filter_margin_fuzz.c re
 kernel's filter arithmetic and the reference's discriminant in all four arithmetic modes and
 checks that claim on adversarial near-tangent cases; the margin factor 48 u must also keep a
 safety factor over the worst case seen (a first-order error bound gives ~30 u).
+
+These fuzzers restate the kernel's arithmetic by hand and model v_rsq_f32 / v_rcp_f32 / v_sqrt_f32 as the
+correctly rounded value +- 1 ulp.  The device's own code runs on the same kind of cases in
+tests/test_gpu_cull_probe.py (nearest_hit and camera_sweep through the ray probe, against a brute-force loop in
+the oracle); what stays modelled here alone is the margins' headroom over 1e7 .. 1e8 cases.
 """
 import os
 import subprocess

@@ -377,3 +377,53 @@ def test_q3_retire_rule_matches_literal(trial):
     for q in range(spp, P):
         ysky[q] = 0.777   # sky(0) stand-in for the zero-direction lanes
     assert _literal(spp, depth, alive, att, ysky) == _retire_rule(spp, depth, alive, att, ysky)
+
+
+# ---- oracle_nearest_hit: the per-ray reference of tests/test_gpu_cull_probe.py ----
+def _nearest(spheres, o, d, mode, dtype):
+    from oracle_bind import oracle_nearest_hit
+    flat = rt.FlatScene([s[:3] for s in spheres], [s[3] for s in spheres], [0] * len(spheres),
+                        [rt.Lambertian((0.5, 0.5, 0.5))])
+    idx, t = oracle_nearest_hit(flat, mode, np.array(o, dtype).T.copy(), np.array(d, dtype).T.copy())
+    return idx.tolist(), t.tolist()
+
+
+NEAREST_MODES = ["packed", "root2", "scalar"]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("mode", NEAREST_MODES)
+def test_nearest_hit_head_on_and_miss(mode, dtype):
+    # a = 4, hb = -10, c = 24, disc = 4: root1 = (10 - 2) / 4 = 2, exact in every mode; the second ray misses.
+    # Five rays: the packed modes take four a call, so the fifth goes through a partial packet.
+    o = [[0, 0, 0]] * 5
+    d = [[0, 0, -2], [0, 1, 0], [0, 0, -1], [0, 0, 1], [0, 0, -2]]
+    idx, t = _nearest([(0, 0, -5, 1)], o, d, mode, dtype)
+    assert idx == [0, -1, 0, -1, 0]
+    assert t == [2.0, math.inf, 4.0, math.inf, 2.0]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("mode", NEAREST_MODES)
+def test_nearest_hit_tie_rule(mode, dtype):
+    # two identical spheres behind a nearer third: update() takes t <= best (the later twin), min_by_key the first
+    twins = [(0, 0, -5, 1), (0, 0, -5, 1)]
+    idx, t = _nearest(twins, [[0, 0, 0]], [[0, 0, -1]], mode, dtype)
+    assert (idx, t) == ([0 if mode == "scalar" else 1], [4.0])
+    idx, t = _nearest([(0, 0, -9, 1)] + twins + [(0, 0, -9, 1)], [[0, 0, 0]], [[0, 0, -1]], mode, dtype)
+    assert (idx, t) == ([1 if mode == "scalar" else 2], [4.0])
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("mode", NEAREST_MODES)
+def test_nearest_hit_root_below_t_min(mode, dtype):
+    # origin 2^-11 outside the surface: oc_z = 1 + 2^-11, c = 2^-10 + 2^-22, disc = 1, all exact in fp32;
+    # root1 = 2^-11 < 0.001 is invalid.  Q1 tests root1 twice (no hit); root2 and scalar take root2 = 2 + 2^-11.
+    idx, t = _nearest([(0, 0, -5, 1)], [[0, 0, -4 + 2.0 ** -11]], [[0, 0, -1]], mode, dtype)
+    if mode == "packed":
+        assert (idx, t) == ([-1], [math.inf])
+    else:
+        assert (idx, t) == ([0], [2 + 2.0 ** -11])
+    # just above t_min: root1 = 2^-9 is valid in every mode
+    idx, t = _nearest([(0, 0, -5, 1)], [[0, 0, -4 + 2.0 ** -9]], [[0, 0, -1]], mode, dtype)
+    assert (idx, t) == ([0], [2.0 ** -9])
