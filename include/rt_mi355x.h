@@ -133,6 +133,10 @@ typedef struct rt_stats {
 /* Set: the guide-buffer kernel ran, guide_pixels<T, CAMQ, MEGA> (rt_render_guides_async); F64, WAVES, CAMQ and
  * MEGA mean what they mean above, ROOT2, MODE, SPLIT and ITEMS are 0. */
 #define RT_KERNEL_GUIDES(id) (((id) >> 11) & 1u)
+/* Set: the ray-query kernel ran, query_rays<T, ROOT2, SHARED, MEGA> (rt_query_hits_async); F64, WAVES, ROOT2 and
+ * MEGA mean what they mean above, CAMQ is SHARED (the shared-origin path: the camera sweep over the origin's camera
+ * tables), MODE, SPLIT, ITEMS and GUIDES are 0. */
+#define RT_KERNEL_QUERY(id) (((id) >> 12) & 1u)
 
 /* ---- flags ---- */
 #define RT_FLAG_F32 0x1u     /* compute in fp32 (default: fp64, the reference's arithmetic) */
@@ -254,6 +258,53 @@ int rt_render_split_async(rt_context* ctx, const rt_camera* camera, uint32_t max
 int rt_render_guides_async(rt_context* ctx, const rt_camera* camera, uint32_t spp, uint64_t seed, uint32_t flags,
                            const rt_tile_range* range, void* d_albedo, void* d_normal, void* d_depth,
                            void* d_coverage, void* stream);
+/* ---- ray queries: the closest hit of caller-supplied rays ----
+ * What is under a pixel of a preview, rays of a camera model the reference lacks (orthographic, fisheye, panorama),
+ * occlusion passes over first hits, an integrator driven from the host's own device tensors: n_rays rays through the
+ * sweeps the renders run, one result per ray.  T is float under RT_FLAG_F32 and double otherwise.
+ * Rays:
+ *   d_directions  device [n_rays][3] of T (the natural (n, 3) tensor).  Directions are NOT normalised.
+ *   origins       exactly one of the two forms (both or neither: RT_ERR_INVALID):
+ *                 per ray: d_origins is device [n_rays][3] of T and origin is NULL;
+ *                 shared:  d_origins is NULL and origin is 3 HOST doubles, rounded to T the way a camera centre is
+ *                          ((T)origin[i]).  The call then runs the camera sweep over the camera tables of that origin,
+ *                          which it builds under rt_render_async's rule (a later render with another centre rebuilds
+ *                          them).  Both forms give the same values for the same rays.
+ * Definition, per ray (o, d), in T:
+ *   hit      the closest hit of the live path over all spheres in scene order: Sphere::hit_packed
+ *            (objects.rs:249-290) plus PackedHitRecords::update (objects.rs:140-155).  t in [0.001, inf); ties go to
+ *            the later sphere; quirk Q1 applies (the near root is tested twice, so a ray whose near root is invalid,
+ *            e.g. one that starts inside a sphere, misses that sphere) unless RT_FLAG_ROOT2, which accepts the far
+ *            root like scalar Sphere::hit.  Picking wants RT_FLAG_ROOT2.
+ *   t        the ray parameter of the hit: the hit point is o + d t, a distance only when |d| = 1.
+ *   then PackedHitRecords::finalize (objects.rs:157-162), as the guide buffers have it:
+ *   point    o + d t (a multiply, then an add: no FMA)
+ *   normal   (point - centre) / sqrt(|point - centre|^2) with the packed (mul_add) length, negated when not front
+ *   front    pk_dot(d, normal) < 0, taken before the negation
+ *   index    the sphere's scene index.
+ *   A miss:  index -1, t +inf, normal and point 0, front 0.
+ * Precondition, enforced per ray: a ray is invalid when a component of its origin or direction is not finite, or
+ * when |d|^2 (PackedVec3::length_squared, in T) is outside [1e-6, 1e6], the constants rounded to T: the range of
+ * direction lengths the culls are proven for; it also excludes a zero direction.  The bounds themselves are valid.
+ * An invalid ray is not traced: index -2 (RT_QUERY_INVALID), t NaN, normal and point 0, front 0, and the results of
+ * the other rays do not depend on it.
+ * Outputs: device pointers, any may be NULL, all of them NULL is RT_ERR_INVALID.  d_t: T [n_rays]; d_index: int32
+ * [n_rays]; d_normal, d_point: T [n_rays][3]; d_front: uint8 [n_rays].  A value does not depend on which other outputs
+ * were asked for.
+ * flags: RT_FLAG_F32 and RT_FLAG_ROOT2.  Any RT_FLAG_MODE_* is RT_ERR_UNSUPPORTED; unknown bits are RT_ERR_INVALID.
+ * n_rays == 0: RT_OK, nothing is enqueued.  n_rays > 0x7FFFFFFF: RT_ERR_UNSUPPORTED.  RT_ERR_INVALID, checked before
+ * any HIP call: ctx or d_directions NULL, no scene set.
+ * Asynchronous on `stream` under rt_render_async's cross-stream rule.  Allowed while a progressive session is open;
+ * touches neither its records nor its counts.
+ * rt_context_collect after it: pixels = n_rays, samples = ray_segments = the valid rays, bounce_iters = 0, lane_slots
+ * 64 per batch of 64 consecutive rays with a valid ray in it, RT_KERNEL_QUERY(kernel_id) is set; the executed-work
+ * counters hold what the reused sweeps count.
+ * Out of scope: sorting or binning incoherent rays, a per-ray t_max or an any-hit exit, the scalar mode, radiance. */
+#define RT_QUERY_MISS (-1)
+#define RT_QUERY_INVALID (-2)
+int rt_query_hits_async(rt_context* ctx, uint64_t n_rays, const void* d_origins, const double* origin,
+                        const void* d_directions, uint32_t flags, void* d_t, void* d_index, void* d_normal,
+                        void* d_point, void* d_front, void* stream);
 /* The plan rt_render_split_async makes for samples_per_item = 0; host only, needs no GPU.
  * resident_waves: the waves the split kernels keep resident (CUs x 4 SIMDs x 5 waves in fp32, x 4 in fp64).
  * Returns the samples per item (a multiple of 128, or spp when the plan is one item per pixel) and the
@@ -420,6 +471,8 @@ int rt_context_collect(rt_context* ctx, void* stream, rt_stats* stats);
 int rt_device_alloc(rt_context* ctx, size_t bytes, void** out);
 int rt_device_free(rt_context* ctx, void* ptr);
 int rt_memcpy_d2h(rt_context* ctx, void* dst, const void* src, size_t bytes);   /* synchronises the device */
+int rt_memcpy_h2d(rt_context* ctx, void* dst, const void* src, size_t bytes);   /* host to device (a query's rays);
+                                                                                    returns when the copy is done */
 
 /* Last error message of the calling thread ("" if none). */
 const char* rt_last_error(void);

@@ -30,15 +30,17 @@
 // Source layout (one translation unit): rt_experiments.hpp (build kinds), rt_formats.hpp (the formats host
 // layout and device code share; no HIP), rt_common.hpp (kernel arguments, scalar-load pipelines),
 // rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (replay + reduction),
-// rt_trace.hpp + rt_trace_body.hpp (the persistent kernel), rt_guides.hpp (guide buffers: first hits only);
+// rt_trace.hpp + rt_trace_body.hpp (the persistent kernel), rt_guides.hpp (guide buffers: first hits only),
+// rt_query.hpp (ray queries: the closest hit of the caller's rays);
 // and, host only, without HIP: rt_layout.hpp (the scene image: every device table of a scene,
 // build_scene_image), rt_split_plan.hpp (the sample-parallel plan), rt_progressive_plan.hpp (a progressive
 // session's record buffer and sample windows).  This file holds the C ABI: the context and its device tables,
 // the launch steps (scene_params, frame_params, ensure_cam_tables, plan_grid) and the launchers (launch_plain,
 // launch_split, launch_window; launch_items and launch_classes for a session's per-pixel counts;
-// launch_guides).
+// launch_guides, launch_query).
 #include "rt_trace.hpp"
 #include "rt_guides.hpp"
+#include "rt_query.hpp"
 #include "rt_layout.hpp"
 #include "rt_split_plan.hpp"
 #include "rt_progressive_plan.hpp"
@@ -194,6 +196,7 @@ struct rt_context {
     DeviceScene<double> d64;
     DeviceBuffer ridx, mtiers;   // slot -> scene index; the mega walk's order table (pack_mega_tiers)
     SceneCounts n;
+    bool has_scene = false;   // rt_context_set_scene has succeeded since the context was made
     template <typename T> DeviceScene<T>& scene() {
         if constexpr (sizeof(T) == 8) return d64; else return d32;
     }
@@ -309,6 +312,7 @@ static void free_scene(rt_context* c) {
     c->ridx.reset();
     c->mtiers.reset();
     c->n = SceneCounts{};
+    c->has_scene = false;
 }
 
 extern "C" int rt_context_destroy(rt_context* c) {
@@ -350,6 +354,7 @@ extern "C" int rt_context_set_scene(rt_context* c, const rt_scene* s) {
         return rc;
     }
     c->n = im.n;
+    c->has_scene = true;
     return RT_OK;
 }
 
@@ -439,6 +444,17 @@ constexpr uint32_t kKernelGuidesBit = 1u << 11;
 template <typename T, bool CAMQ>
 static void (*pick_guides(bool mega))(GParams<T>) {
     return mega ? guide_pixels<T, CAMQ, true> : guide_pixels<T, CAMQ, false>;
+}
+// The ray-query kernel (rt_query_hits_async): query_rays<T, ROOT2, SHARED, MEGA> (RT_KERNEL_QUERY in the kernel id).
+constexpr uint32_t kKernelQueryBit = 1u << 12;
+template <typename T, bool ROOT2, bool SHARED>
+static void (*pick_query(bool mega))(QParams<T>) {
+    return mega ? query_rays<T, ROOT2, SHARED, true> : query_rays<T, ROOT2, SHARED, false>;
+}
+template <typename T>
+static void (*pick_query(bool root2, bool shared, bool mega))(QParams<T>) {
+    if (root2) return shared ? pick_query<T, true, true>(mega) : pick_query<T, true, false>(mega);
+    return shared ? pick_query<T, false, true>(mega) : pick_query<T, false, false>(mega);
 }
 constexpr uint64_t kScratchBudget = 24ull << 30;   // scratch (and record buffer) bytes a launch may ask for
 
@@ -703,6 +719,62 @@ static int launch_guides(rt_context* c, const FrameArgs& a, float* albedo, float
     gp.depth = depth;
     gp.coverage = coverage;
     hipLaunchKernelGGL(gfn, dim3((uint32_t)nblocks), dim3(256), 0, st, gp);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// What rt_query_hits_async asks for: the rays (origins: device, per ray; or origin: host, shared) and the outputs.
+struct QueryArgs {
+    uint64_t n_rays;
+    const void* origins;
+    const double* origin;
+    const void* directions;
+    uint32_t flags;
+    void *t, *index, *normal, *point, *front;
+};
+
+// query_rays: the waves stride over the batches of 64 consecutive rays.  No scratch, no records, no claim counter.
+// A shared origin is a camera centre to the tables: KParams points at the camera tables of that origin, which are
+// rebuilt under a render's key rule (so a later render with another centre rebuilds them in turn).  An origin that
+// is not finite in T makes every ray invalid and no sweep runs: its tables are not built, and the key stays.
+template <typename T>
+static int launch_query(rt_context* c, const QueryArgs& a, hipStream_t st) {
+    KParams<T> p;
+    memset(&p, 0, sizeof(p));
+    scene_params(c, p);
+    const char* e = getenv("RT_FILTER_OFF");   // diagnostics, as frame_setup has it
+    const bool filter_off = e && atoi(e) != 0;
+    if (filter_off) p.f_cmax = std::numeric_limits<float>::infinity();
+    p.flags = a.flags;
+    p.n_items = (uint32_t)a.n_rays;
+    const bool shared = a.origin != nullptr, root2 = (a.flags & RT_FLAG_ROOT2) != 0u, mega = p.n_mg > 0;
+    int rc = RT_OK;
+    if (shared) {
+        bool finite = true;
+        for (int i = 0; i < 3; ++i) {
+            p.center[i] = (T)a.origin[i];
+            finite = finite && std::isfinite(p.center[i]);
+        }
+        if (finite && (rc = ensure_cam_tables(c, p, a.flags, filter_off, st)) != RT_OK) return rc;
+    }
+    void (*const qfn)(QParams<T>) = pick_query<T>(root2, shared, mega);
+    constexpr int W = kWavesQuery<T>;
+    const uint32_t id = 0x8000u | (sizeof(T) == 8 ? 1u : 0u) | ((uint32_t)W << 1) | (root2 ? 1u << 4 : 0u) |
+                        (shared ? 1u << 7 : 0u) | (mega ? 1u << 8 : 0u) | kKernelQueryBit;
+    const uint32_t n_batches = (uint32_t)((a.n_rays + 63u) / 64u);   // a wave's work item
+    uint64_t nblocks = 0;
+    if ((rc = plan_grid(c, (const void*)qfn, W, id, n_batches, 1u, nblocks, p.blk_g)) != RT_OK) return rc;
+    QParams<T> qp;
+    memset(&qp, 0, sizeof(qp));
+    qp.k = p;
+    qp.origins = (const T*)a.origins;
+    qp.directions = (const T*)a.directions;
+    qp.t = (T*)a.t;
+    qp.index = (int32_t*)a.index;
+    qp.normal = (T*)a.normal;
+    qp.point = (T*)a.point;
+    qp.front = (uint8_t*)a.front;
+    hipLaunchKernelGGL(qfn, dim3((uint32_t)nblocks), dim3(256), 0, st, qp);
     HIPCHK(hipGetLastError());
     return RT_OK;
 }
@@ -1034,6 +1106,29 @@ extern "C" int rt_render_guides_async(rt_context* c, const rt_camera* cam, uint3
                                : launch_guides<double>(c, a, (float*)d_albedo, (float*)d_normal, (float*)d_depth, (float*)d_coverage, st);
     if (rc != RT_OK) return rc;
     return end_launch(c, st, n_pix, n_pix * spp);
+}
+
+extern "C" int rt_query_hits_async(rt_context* c, uint64_t n_rays, const void* d_origins, const double* origin,
+                                   const void* d_directions, uint32_t flags, void* d_t, void* d_index, void* d_normal,
+                                   void* d_point, void* d_front, void* stream) {
+    const std::string who = "rt_query_hits_async";
+    if (!c || !d_directions) return fail(RT_ERR_INVALID, who + ": NULL argument (ctx or d_directions)");
+    if ((d_origins != nullptr) == (origin != nullptr))
+        return fail(RT_ERR_INVALID, who + ": exactly one of d_origins (per ray) and origin (shared) must be given");
+    if (!d_t && !d_index && !d_normal && !d_point && !d_front) return fail(RT_ERR_INVALID, who + ": all five outputs are NULL");
+    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
+    if (flags & ~(RT_FLAG_F32 | RT_FLAG_ROOT2))
+        return fail(RT_ERR_UNSUPPORTED, who + ": the live path's hit only (RT_FLAG_F32, RT_FLAG_ROOT2; no RT_FLAG_MODE_*)");
+    if (n_rays > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many rays in one call");
+    if (!c->has_scene) return fail(RT_ERR_INVALID, who + ": no scene set (rt_context_set_scene first)");
+    if (n_rays == 0) return RT_OK;
+    const QueryArgs a{n_rays, d_origins, origin, d_directions, flags, d_t, d_index, d_normal, d_point, d_front};
+    hipStream_t st = (hipStream_t)stream;
+    int rc = begin_launch(c, st);
+    if (rc != RT_OK) return rc;
+    rc = (flags & RT_FLAG_F32) ? launch_query<float>(c, a, st) : launch_query<double>(c, a, st);
+    if (rc != RT_OK) return rc;
+    return end_launch(c, st, n_rays, 0u);   // samples: the valid rays, counted on the device (kQuerySlot)
 }
 
 extern "C" int rt_split_plan(uint64_t n_pixels, uint32_t spp, uint32_t resident_waves, uint32_t* samples_per_item,
@@ -1551,7 +1646,7 @@ extern "C" int rt_context_collect(rt_context* c, void* stream, rt_stats* out) {
     if (c->have_first) HIPCHK(hipEventElapsedTime(&ms, c->ev_first, c->ev_last));
     HIPCHK(hipMemset(c->segs.p, 0, segs.size() * sizeof(unsigned long long)));
     HIPCHK(hipMemset(c->err.p, 0, 16));
-    uint64_t total = 0, slots = 0, iters = 0, dsky = 0, kst[kNKstat] = {}, work[kNWork] = {};
+    uint64_t total = 0, slots = 0, iters = 0, dsky = 0, qrays = 0, kst[kNKstat] = {}, work[kNWork] = {};
     for (int i = 0; i < kSegShards; ++i)
         for (int j = 0; j < kNKstat; ++j) kst[j] += segs[(size_t)i * kSegStride + kstat_slot(j)];
     if (kst[0] | kst[1] | kst[2] | kst[3]) {   // instrumented build (make kstats) only
@@ -1570,13 +1665,14 @@ extern "C" int rt_context_collect(rt_context* c, void* stream, rt_stats* out) {
         slots += segs[(size_t)i * kSegStride + 1];
         iters += segs[(size_t)i * kSegStride + 2];
         dsky += segs[(size_t)i * kSegStride + kDirectSkySlot];
+        qrays += segs[(size_t)i * kSegStride + kQuerySlot];   // the valid rays of the queries
         for (uint32_t j = 0; j < kNWork; ++j) work[j] += segs[(size_t)i * kSegStride + kWorkSlot + j];
     }
     if (out) {
         memset(out, 0, sizeof(*out));
         out->kernel_ms = ms;
         out->pixels = c->pixels;
-        out->samples = c->samples;
+        out->samples = c->samples + qrays;
         out->ray_segments = total;
         out->lane_slots = slots;
         out->bounce_iters = iters;
@@ -1614,6 +1710,13 @@ extern "C" int rt_memcpy_d2h(rt_context* c, void* dst, const void* src, size_t b
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+extern "C" int rt_memcpy_h2d(rt_context* c, void* dst, const void* src, size_t bytes) {
+    if (!c || !dst || !src) return fail(RT_ERR_INVALID, "rt_memcpy_h2d: NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     return RT_OK;
 }
 

@@ -4,6 +4,7 @@
 //             [--seed 0x5EED0001] [--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar]
 //             [--out output.png|.ppm] [--block-size B] [--sample-parallel] [--progressive n1,n2,...]
 //             [--adaptive TOL --spp-min N [--count-map counts.png|.ppm] [--device-plan]] [--guides] [--dump-scene]
+//             [--pick COL,ROW]...
 //
 // --mode picks which of the reference's renderers is reproduced (include/rt_mi355x.h): the live
 // render_vectorized2 (default), render_vectorized, or the scalar render.
@@ -25,6 +26,14 @@
 // one, scale -1.0, little-endian, rows bottom to top).  They are always the uniform guides at --spp, from the
 // primary rays of the image at --spp, whatever way the image itself was sampled; --out is the file the command
 // writes without --guides.  One line gives the guide pass's kernel time and sample rate.  The live path only.
+//
+// --pick COL,ROW (repeatable) renders nothing and writes no file: it asks what lies under the centre of each of those
+// pixels of the --width x --height frame (rt_query_hits_async: the ray from the camera centre through the pixel
+// centre, quirk Q1 off so that a camera inside a sphere picks it, in fp64 or with --f32 in fp32) and prints one line
+// per pick: "Pick (COL, ROW): sphere I KIND t T point [X, Y, Z] normal [X, Y, Z] front F" or "Pick (COL, ROW): miss",
+// the numbers with enough digits to round-trip.  --mode vectorized2 only, and not with an option that says how or
+// where an image is rendered (--out, --block-size, --sample-parallel, --progressive, --adaptive, --guides): each is
+// refused.  --root2 is what a pick does anyway and is accepted; --spp, --bounces and --seed have no effect.
 //
 // Defaults are main.rs's hard-coded values (scene.toml in the working directory, 3840x2160, 50
 // bounces, 100 spp, camera from (16,2,18.5) looking at the origin, vfov 30, focal 10, no defocus,
@@ -88,7 +97,8 @@ int main(int argc, char** argv) {
     std::string scene_path = "scene.toml", out = "output.png";
     uint32_t width = 3840, height = 2160, spp = 100, bounces = 50, flags = 0, block_size = 0;
     uint64_t seed = 0x5EED0001ull;
-    bool dump = false, sample_parallel = false, guides = false;
+    bool dump = false, sample_parallel = false, guides = false, out_given = false;
+    std::vector<std::pair<uint32_t, uint32_t>> picks;   // --pick: (col, row)
     std::string progressive_arg, count_map;
     bool progressive = false, adaptive = false, device_plan = false;
     double tolerance = 0.0;
@@ -115,7 +125,7 @@ int main(int argc, char** argv) {
             else if (m == "scalar") flags |= RT_FLAG_MODE_SCALAR;
             else if (m != "vectorized2") { std::fprintf(stderr, "unknown mode %s\n", m.c_str()); return 2; }
         }
-        else if (a == "--out") out = next();
+        else if (a == "--out") { out = next(); out_given = true; }
         else if (a == "--block-size") block_size = (uint32_t)std::stoul(next());
         else if (a == "--sample-parallel") sample_parallel = true;
         else if (a == "--progressive") { progressive_arg = next(); progressive = true; }
@@ -124,12 +134,24 @@ int main(int argc, char** argv) {
         else if (a == "--count-map") count_map = next();
         else if (a == "--device-plan") device_plan = true;
         else if (a == "--guides") guides = true;
+        else if (a == "--pick") {
+            const std::string v = next();
+            const size_t comma = v.find(',');
+            auto digits = [](const std::string& t) {
+                return !t.empty() && t.size() <= 9 && t.find_first_not_of("0123456789") == std::string::npos;
+            };
+            if (comma == std::string::npos || !digits(v.substr(0, comma)) || !digits(v.substr(comma + 1))) {
+                std::fprintf(stderr, "--pick: '%s' is not COL,ROW\n", v.c_str());
+                return 2;
+            }
+            picks.emplace_back((uint32_t)std::stoul(v.substr(0, comma)), (uint32_t)std::stoul(v.substr(comma + 1)));
+        }
         else if (a == "--dump-scene") dump = true;
         else if (a == "-h" || a == "--help") {
             std::puts("rt-render [--scene scene.toml] [--width W] [--height H] [--spp S] [--bounces B] [--seed N] "
                       "[--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar] [--out output.png] [--block-size B] "
                       "[--sample-parallel] [--progressive n1,n2,...] [--adaptive TOL --spp-min N [--count-map PATH] "
-                      "[--device-plan]] [--guides] [--dump-scene]");
+                      "[--device-plan]] [--guides] [--dump-scene] [--pick COL,ROW]...");
             return 0;
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -186,6 +208,21 @@ int main(int argc, char** argv) {
             return bad("only with --mode vectorized2: the guides are the live path's first hits");
         if (block_size != 0) return bad("not with --block-size: the guide pass is one launch over the whole image");
     }
+    if (!picks.empty()) {
+        auto bad = [](const std::string& why) {
+            std::fprintf(stderr, "--pick: %s\n", why.c_str());
+            return 2;
+        };
+        if (flags & (RT_FLAG_MODE_VECTORIZED | RT_FLAG_MODE_SCALAR | RT_FLAG_MODE_VECTORIZED3))
+            return bad("only with --mode vectorized2: a query is the live path's closest hit");
+        if (progressive || adaptive || guides || sample_parallel || block_size != 0 || out_given)
+            return bad("not with --out, --block-size, --sample-parallel, --progressive, --adaptive or --guides: nothing is "
+                       "rendered and no file is written");
+        for (const auto& p : picks)
+            if (p.first >= width || p.second >= height)
+                return bad("(" + std::to_string(p.first) + ", " + std::to_string(p.second) + ") is outside the " +
+                           std::to_string(width) + " x " + std::to_string(height) + " frame");
+    }
     try {
         std::ifstream in(scene_path, std::ios::binary);   // main.rs:31-34
         if (!in) throw Panic("Can't read scene from file " + scene_path);
@@ -210,6 +247,21 @@ int main(int argc, char** argv) {
         std::printf("\t Number of objects: \t %zu\n", scene.len());                           // main.rs:60
 
         GpuRenderer renderer(seed, flags, block_size, sample_parallel);   // block_size 128: TileRenderer::new(None, 128), main.rs:62
+        if (!picks.empty()) {
+            static const char* const kinds[3] = {"lambertian", "metal", "dielectric"};
+            const int digits = (flags & RT_FLAG_F32) ? 9 : 17;
+            for (const GpuRenderer::Pick& p : renderer.pick(picks, scene, camera)) {
+                if (p.index < 0) {
+                    std::printf("Pick (%u, %u): %s\n", p.col, p.row, p.index == RT_QUERY_MISS ? "miss" : "invalid");
+                    continue;
+                }
+                std::printf("Pick (%u, %u): sphere %d %s t %.*g point [%.*g, %.*g, %.*g] normal [%.*g, %.*g, %.*g] front %d\n",
+                            p.col, p.row, p.index, kinds[p.kind < 3 ? p.kind : 0], digits, p.t, digits, p.point[0], digits,
+                            p.point[1], digits, p.point[2], digits, p.normal[0], digits, p.normal[1], digits, p.normal[2],
+                            p.front ? 1 : 0);
+            }
+            return 0;
+        }
         std::fprintf(stderr, "Rendering %u by %u image on %s (%s)...\n", width, height, rt_version(),
                      (flags & RT_FLAG_F32) ? "fp32" : "fp64");
         auto step = [&](uint32_t n, const RgbImage& im, const rt_stats& so_far, bool range_err) {

@@ -499,6 +499,85 @@ struct GpuRenderer : Renderer {
         return g;
     }
 
+    // Picking (rt_query_hits_async): what lies under the centre of each pixel (col, row) of `pixels`.  The ray starts
+    // at the camera centre and goes through the pixel centre, Camera::get_ray (ray_tracing.rs:77-84) with both jitter
+    // draws at 0.5 and no defocus offset, computed here in the render's precision T; the shared-origin path with
+    // RT_FLAG_ROOT2 (a camera inside a sphere picks that sphere).  One launch on a context of its own.
+    struct Pick {
+        uint32_t col = 0, row = 0;
+        int32_t index = -1;          // scene index; RT_QUERY_MISS, RT_QUERY_INVALID
+        uint32_t kind = 0;           // the hit sphere's material kind
+        double t = 0, point[3] = {0, 0, 0}, normal[3] = {0, 0, 0};
+        bool front = false;
+    };
+    template <typename T>
+    std::vector<Pick> pick_t(const std::vector<std::pair<uint32_t, uint32_t>>& pixels, const Scene& scene,
+                             const Camera& camera) {
+        FlatScene flat = scene.flatten();
+        rt_scene rs = flat.view();
+        const size_t n = pixels.size();
+        const rt_camera& c = camera.c;
+        std::vector<T> dir(3 * n);
+        for (size_t i = 0; i < n; ++i) {
+            const T fx = ((T)pixels[i].first + T(0.5)) / (T)c.image_width;     // ray_tracing.rs:78-80
+            const T fy = ((T)pixels[i].second + T(0.5)) / (T)c.image_height;
+            T v[3];
+            for (int a = 0; a < 3; ++a) {
+                const T off = (T)c.vu[a] * fx + (T)c.vv[a] * fy;
+                const T pc = (T)c.ulc[a] + off;                                 // :81
+                v[a] = pc - (T)c.center[a];                                     // :84
+            }
+            const T len = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);   // unit_vector, no FMA
+            for (int a = 0; a < 3; ++a) dir[3 * i + a] = v[a] / len;
+        }
+        struct Ctx {
+            rt_context* c = nullptr;
+            void* buf[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            ~Ctx() {
+                for (void* b : buf) if (b) rt_device_free(c, b);
+                if (c) rt_context_destroy(c);
+            }
+        } x;
+        auto chk = [](int rc, const char* what) {
+            if (rc != RT_OK) throw Panic(std::string(what) + ": " + rt_last_error());
+        };
+        chk(rt_context_create(0, &x.c), "rt_context_create");
+        chk(rt_context_set_scene(x.c, &rs), "rt_context_set_scene");
+        const size_t bytes[6] = {3 * n * sizeof(T), n * sizeof(T), n * sizeof(int32_t), 3 * n * sizeof(T), 3 * n * sizeof(T), n};
+        for (int i = 0; i < 6; ++i) chk(rt_device_alloc(x.c, bytes[i], &x.buf[i]), "rt_device_alloc");
+        std::vector<Pick> out(n);
+        if (n == 0) return out;
+        chk(rt_memcpy_h2d(x.c, x.buf[0], dir.data(), bytes[0]), "rt_memcpy_h2d");
+        const uint32_t qflags = (flags & RT_FLAG_F32) | RT_FLAG_ROOT2;
+        chk(rt_query_hits_async(x.c, n, nullptr, c.center, x.buf[0], qflags, x.buf[1], x.buf[2], x.buf[3], x.buf[4],
+                                x.buf[5], nullptr),
+            "rt_query_hits_async");
+        chk(rt_context_collect(x.c, nullptr, nullptr), "rt_context_collect");
+        std::vector<T> t(n), nrm(3 * n), pnt(3 * n);
+        std::vector<int32_t> idx(n);
+        std::vector<uint8_t> fr(n);
+        chk(rt_memcpy_d2h(x.c, t.data(), x.buf[1], bytes[1]), "rt_memcpy_d2h");
+        chk(rt_memcpy_d2h(x.c, idx.data(), x.buf[2], bytes[2]), "rt_memcpy_d2h");
+        chk(rt_memcpy_d2h(x.c, nrm.data(), x.buf[3], bytes[3]), "rt_memcpy_d2h");
+        chk(rt_memcpy_d2h(x.c, pnt.data(), x.buf[4], bytes[4]), "rt_memcpy_d2h");
+        chk(rt_memcpy_d2h(x.c, fr.data(), x.buf[5], bytes[5]), "rt_memcpy_d2h");
+        for (size_t i = 0; i < n; ++i) {
+            Pick& p = out[i];
+            p.col = pixels[i].first;
+            p.row = pixels[i].second;
+            p.index = idx[i];
+            p.kind = idx[i] >= 0 ? flat.materials[flat.material[(size_t)idx[i]]].kind : 0u;
+            p.t = (double)t[i];
+            for (int a = 0; a < 3; ++a) { p.point[a] = (double)pnt[3 * i + a]; p.normal[a] = (double)nrm[3 * i + a]; }
+            p.front = fr[i] != 0;
+        }
+        return out;
+    }
+    std::vector<Pick> pick(const std::vector<std::pair<uint32_t, uint32_t>>& pixels, const Scene& scene,
+                           const Camera& camera) {
+        return (flags & RT_FLAG_F32) ? pick_t<float>(pixels, scene, camera) : pick_t<double>(pixels, scene, camera);
+    }
+
   private:
     void render_blocks(const rt_scene& rs, const Camera& camera, uint32_t max_bounces, uint32_t spp, RgbImage& img,
                        rt_stats& total, uint32_t B, bool print_blocks) {

@@ -91,6 +91,15 @@ def RT_KERNEL_GUIDES(kernel_id):
     return (kernel_id >> 11) & 1
 
 
+def RT_KERNEL_QUERY(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_QUERY: the ray-query kernel ran (rt_query_hits_async)."""
+    return (kernel_id >> 12) & 1
+
+
+RT_QUERY_MISS = -1      # include/rt_mi355x.h: rt_query_hits_async's index of a ray that hits nothing
+RT_QUERY_INVALID = -2   # ... and of a ray outside the precondition (not traced)
+
+
 def kernel_info(kernel_id):
     """rt_stats.kernel_id decoded (include/rt_mi355x.h RT_KERNEL_*): the trace_paths instantiation that ran."""
     if kernel_id == 0:
@@ -98,7 +107,7 @@ def kernel_info(kernel_id):
     return {"T": "double" if kernel_id & 1 else "float", "W": (kernel_id >> 1) & 7, "root2": bool((kernel_id >> 4) & 1),
             "mode": (kernel_id >> 5) & 3, "camq": bool((kernel_id >> 7) & 1), "mega": bool((kernel_id >> 8) & 1),
             "split": bool(RT_KERNEL_SPLIT(kernel_id)), "items": bool(RT_KERNEL_ITEMS(kernel_id)),
-            "guides": bool(RT_KERNEL_GUIDES(kernel_id))}
+            "guides": bool(RT_KERNEL_GUIDES(kernel_id)), "query": bool(RT_KERNEL_QUERY(kernel_id))}
 
 
 def kernel_name(kernel_id):
@@ -107,6 +116,8 @@ def kernel_name(kernel_id):
     if k is None:
         return None
     b = lambda v: "true" if v else "false"
+    if k["query"]:   # query_rays<T,ROOT2,SHARED,MEGA> (SHARED in the CAMQ bit)
+        return f"query_rays<{k['T']},{b(k['root2'])},{b(k['camq'])},{b(k['mega'])}>"
     if k["guides"]:   # guide_pixels<T,CAMQ,MEGA>
         return f"guide_pixels<{k['T']},{b(k['camq'])},{b(k['mega'])}>"
     if k["items"]:   # trace_paths_items<T,W,CAMQ,MEGA> (finish_window_list<T> follows it)
@@ -144,7 +155,7 @@ EXPORTED = [
     "rt_progressive_bytes", "rt_progressive_begin", "rt_progressive_extend_async", "rt_progressive_end",
     "rt_progressive_extend_map_async", "rt_progressive_snapshot_map_async", "rt_progressive_counts",
     "rt_progressive_error_async", "rt_progressive_map_plan", "rt_progressive_refine", "rt_progressive_refine_items",
-    "rt_render_guides_async",
+    "rt_render_guides_async", "rt_query_hits_async", "rt_memcpy_h2d",
 ]
 
 _lib = None
@@ -152,7 +163,7 @@ _lib = None
 # The sources the Makefile hashes into rt_version() ("src=<hash>"), in its order (SRC, then HDR).
 KERNEL_SOURCES = ["rt_kernel.hip", "rt_experiments.hpp", "rt_formats.hpp", "rt_common.hpp", "rt_sweep.hpp",
                   "rt_camera.hpp", "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp",
-                  "rt_progressive_plan.hpp", "rt_guides.hpp"]
+                  "rt_progressive_plan.hpp", "rt_guides.hpp", "rt_query.hpp"]
 SOURCE_FILES = [os.path.join(PKG_DIR, "csrc", f) for f in KERNEL_SOURCES] + \
                [os.path.join(os.path.dirname(PKG_DIR), "include", "rt_mi355x.h")]
 
@@ -206,6 +217,7 @@ def load_library(path=None):
     lib.rt_render_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp]
     lib.rt_render_split_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp, u32]
     lib.rt_render_guides_async.argtypes = [vp, P(RtCamera), u32, u64, u32, P(RtTileRange), vp, vp, vp, vp, vp]
+    lib.rt_query_hits_async.argtypes = [vp, u64, vp, P(f64), vp, u32, vp, vp, vp, vp, vp, vp]
     lib.rt_split_plan.argtypes = [u64, u32, u32, P(u32), P(u64)]
     lib.rt_progressive_bytes.argtypes = [u64, u32, u32, u32, P(u64)]
     lib.rt_progressive_begin.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), u64]
@@ -222,6 +234,7 @@ def load_library(path=None):
     lib.rt_device_alloc.argtypes = [vp, ctypes.c_size_t, P(vp)]
     lib.rt_device_free.argtypes = [vp, vp]
     lib.rt_memcpy_d2h.argtypes = [vp, vp, vp, ctypes.c_size_t]
+    lib.rt_memcpy_h2d.argtypes = [vp, vp, vp, ctypes.c_size_t]
     lib.rt_last_error.restype = ctypes.c_char_p
     lib.rt_version.restype = ctypes.c_char_p
     if path is None:

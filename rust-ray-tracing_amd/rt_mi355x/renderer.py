@@ -88,6 +88,116 @@ GUIDE_CHANNELS = {"albedo": 3, "normal": 3, "depth": 1, "coverage": 1}
 Guides = collections.namedtuple("Guides", GUIDE_NAMES)
 
 
+# Ray-query outputs (rt_query_hits_async), in the C ABI's argument order: name -> (components per ray, dtype; None:
+# the rays' precision).
+QUERY_NAMES = ("t", "index", "normal", "point", "front")
+QUERY_OUTPUTS = {"t": (1, None), "index": (1, np.int32), "normal": (3, None), "point": (3, None), "front": (1, np.uint8)}
+
+
+def _query_dtype(flags):
+    return np.dtype(np.float32 if flags & abi.RT_FLAG_F32 else np.float64)
+
+
+def _query_shape(name, n):
+    return (n, 3) if QUERY_OUTPUTS[name][0] == 3 else (n,)
+
+
+def check_query(flags, origins, directions, want=QUERY_NAMES):
+    """GpuRenderer.query's arguments checked before any GPU call: the live path's hit only (no mode flag), known
+    output names, directions (n, 3) and origins (n, 3) or (3,) of finite-or-not numbers (the library judges each
+    ray).  Returns (origins, directions, shared, want) with the arrays contiguous in the renderer's precision;
+    shared: origins has shape (3,) and is kept in float64 (the library rounds it the way it rounds a camera centre)."""
+    if flags & ~(abi.RT_FLAG_F32 | abi.RT_FLAG_ROOT2):
+        raise ValueError("ray queries are the live path's closest hit: mode 'vectorized2' only (root2 is allowed)")
+    want = tuple(want)
+    for name in want:
+        if name not in QUERY_NAMES:
+            raise ValueError(f"unknown query output {name!r} (one of {list(QUERY_NAMES)})")
+    if not want:
+        raise ValueError("no query output asked for")
+    dtype = _query_dtype(flags)
+    d = np.asarray(directions)
+    o = np.asarray(origins)
+    for what, a in (("directions", d), ("origins", o)):
+        if a.dtype.kind not in "fiu":
+            raise ValueError(f"{what} must be numbers, not dtype {a.dtype}")
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError(f"directions must have shape (n, 3), not {d.shape}")
+    shared = o.shape == (3,)
+    if not shared and o.shape != d.shape:
+        raise ValueError(f"origins must have shape (3,) (one shared origin) or {d.shape} like directions, not {o.shape}")
+    if d.shape[0] > 0x7FFFFFFF:
+        raise ValueError("more than 0x7FFFFFFF rays in one query")
+    o = np.ascontiguousarray(o, dtype=np.float64 if shared else dtype)
+    return o, np.ascontiguousarray(d, dtype=dtype), shared, want
+
+
+def _device_array(obj, what, dtype, shape, device):
+    """The device pointer of obj, an object exposing __cuda_array_interface__ (a torch ROCm tensor does), after
+    checking dtype, shape, contiguity, writability where it is an output (shape given as an output's) and, where the
+    object names one (torch's .device), the device."""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise TypeError(f"{what} must expose __cuda_array_interface__ (a device array), not {type(obj).__name__}")
+    if np.dtype(cai["typestr"]) != np.dtype(dtype):
+        raise ValueError(f"{what} must have dtype {np.dtype(dtype).name}, not {np.dtype(cai['typestr']).name}")
+    if tuple(cai["shape"]) != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}, not {tuple(cai['shape'])}")
+    strides = cai.get("strides")
+    if strides is not None:
+        expect, step = [], np.dtype(dtype).itemsize
+        for k in reversed(shape):
+            expect.insert(0, step)
+            step *= max(k, 1)
+        if any(s != e for s, e, k in zip(strides, expect, shape) if k > 1):
+            raise ValueError(f"{what} must be C-contiguous (strides {tuple(strides)})")
+    dev = getattr(obj, "device", None)
+    if dev is not None and hasattr(dev, "type"):
+        if dev.type != "cuda" or (dev.index is not None and dev.index != device):
+            raise ValueError(f"{what} is on {dev}, the renderer's context on device {device}")
+    ptr = cai["data"][0]
+    if not ptr and int(np.prod(shape)):
+        raise ValueError(f"{what} has a NULL data pointer")
+    return ptr
+
+
+def check_query_into(flags, device, origins, directions, outputs):
+    """GpuRenderer.query_into's arguments checked before any GPU call.  Returns (n, d_origins | None, origin | None,
+    d_directions, {name: pointer})."""
+    if flags & ~(abi.RT_FLAG_F32 | abi.RT_FLAG_ROOT2):
+        raise ValueError("ray queries are the live path's closest hit: mode 'vectorized2' only (root2 is allowed)")
+    dtype = _query_dtype(flags)
+    cai = getattr(directions, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise TypeError(f"directions must expose __cuda_array_interface__ (a device array), not {type(directions).__name__}")
+    shape = tuple(cai["shape"])
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"directions must have shape (n, 3), not {shape}")
+    n = shape[0]
+    if n > 0x7FFFFFFF:
+        raise ValueError("more than 0x7FFFFFFF rays in one query")
+    d_dir = _device_array(directions, "directions", dtype, (n, 3), device)
+    d_org, origin = None, None
+    if hasattr(origins, "__cuda_array_interface__"):
+        d_org = _device_array(origins, "origins", dtype, (n, 3), device)
+    else:
+        origin = np.asarray(origins)
+        if origin.shape != (3,) or origin.dtype.kind not in "fiu":
+            raise ValueError("origins must be a device array of shape (n, 3) or one shared origin of 3 host numbers")
+        origin = np.ascontiguousarray(origin, dtype=np.float64)
+    ptrs = {}
+    for name, obj in outputs.items():
+        if obj is None:
+            continue
+        cw = getattr(obj, "__cuda_array_interface__", None)
+        if isinstance(cw, dict) and cw["data"][1]:
+            raise ValueError(f"{name} is read-only")
+        ptrs[name] = _device_array(obj, name, QUERY_OUTPUTS[name][1] or dtype, _query_shape(name, n), device)
+    if not ptrs:
+        raise ValueError("no query output given")
+    return n, d_org, origin, d_dir, ptrs
+
+
 def check_adaptive(spp_min, spp_max, tolerance, plan="host"):
     """GpuRenderer.adaptive's arguments checked before any GPU call: 1 <= spp_min <= spp_max, a tolerance that is
     a number (not NaN), a plan that is "host" or "device".  Returns (spp_min, spp_max, tolerance) as
@@ -442,6 +552,74 @@ class GpuRenderer(Renderer):
         g = Guides(out["albedo"].reshape(h, w, 3), out["normal"].reshape(h, w, 3), out["depth"].reshape(h, w),
                    out["coverage"].reshape(h, w))
         return g, RenderStat(dt, w * h, st.kernel_ms, st.samples, st.ray_segments)
+
+    def _query_flags(self, root2):
+        return self.flags | (abi.RT_FLAG_ROOT2 if root2 else 0)
+
+    def query(self, origins, directions, scene, root2=False, want=QUERY_NAMES):
+        """rt_query_hits_async with numpy arrays: the closest hit of each ray (include/rt_mi355x.h has the
+        definition).  directions: (n, 3), not normalised; origins: (n, 3), or (3,) for one shared origin (the camera
+        sweep over that origin's tables: the same values, and no origins to upload or read).  The arrays are
+        converted to the renderer's precision.  root2: quirk Q1 off, what picking wants (a ray that starts inside a
+        sphere then hits it from the inside); a renderer made with root2=True always has it.
+        Returns {name: array} for the names in `want`: t (n,) and normal, point (n, 3) in the renderer's precision,
+        index (n,) int32 (abi.RT_QUERY_MISS = -1: no hit; abi.RT_QUERY_INVALID = -2: a ray outside the precondition,
+        not traced, its t NaN), front (n,) uint8.  The call's RtStats are kept in self.query_stats."""
+        flags = self._query_flags(root2)
+        o, d, shared, want = check_query(flags, origins, directions, want)   # before any GPU call
+        n = d.shape[0]
+        dtype = d.dtype
+        out = {name: np.empty(_query_shape(name, n), dtype=QUERY_OUTPUTS[name][1] or dtype) for name in want}
+        flat = scene.flatten() if hasattr(scene, "flatten") else scene
+        lib = self.lib
+        if self._scene_flat is not flat:
+            self.set_scene(flat)
+        if n == 0:
+            self.query_stats = abi.RtStats()
+            return out
+        dev = {name: ctypes.c_void_p() for name in want}
+        d_dir, d_org = ctypes.c_void_p(), ctypes.c_void_p()
+        try:
+            abi.check(lib, lib.rt_device_alloc(self.ctx, d.nbytes, ctypes.byref(d_dir)))
+            abi.check(lib, lib.rt_memcpy_h2d(self.ctx, d_dir, d.ctypes.data, d.nbytes))
+            if not shared:
+                abi.check(lib, lib.rt_device_alloc(self.ctx, o.nbytes, ctypes.byref(d_org)))
+                abi.check(lib, lib.rt_memcpy_h2d(self.ctx, d_org, o.ctypes.data, o.nbytes))
+            for name in want:
+                abi.check(lib, lib.rt_device_alloc(self.ctx, out[name].nbytes, ctypes.byref(dev[name])))
+            origin = o.ctypes.data_as(ctypes.POINTER(abi.f64)) if shared else None
+            abi.check(lib, lib.rt_query_hits_async(self.ctx, n, None if shared else d_org, origin, d_dir, flags,
+                                                   *[dev.get(name) for name in QUERY_NAMES], None))
+            st = abi.RtStats()
+            abi.check(lib, lib.rt_context_collect(self.ctx, None, ctypes.byref(st)))
+            self.query_stats = st
+            for name in want:
+                abi.check(lib, lib.rt_memcpy_d2h(self.ctx, out[name].ctypes.data, dev[name], out[name].nbytes))
+        finally:
+            for p in [d_dir, d_org] + list(dev.values()):
+                if p:
+                    lib.rt_device_free(self.ctx, p)
+        return out
+
+    def query_into(self, origins, directions, *, t=None, index=None, normal=None, point=None, front=None, stream=None,
+                   root2=False):
+        """rt_query_hits_async on device arrays in place, without a copy: directions (n, 3) and every output given
+        are objects exposing __cuda_array_interface__ (torch ROCm tensors do) in the renderer's precision, C-contiguous,
+        on the renderer's device; index is int32 and front uint8.  origins: such an array of shape (n, 3), or 3 host
+        numbers for one shared origin.  The scene is the one last set (set_scene).  stream: an integer stream handle
+        such as torch.cuda.current_stream().cuda_stream (None: the null stream); the call is asynchronous on it, so
+        the caller orders its own reads after it on that stream.  Returns the number of rays."""
+        flags = self._query_flags(root2)
+        n, d_org, origin, d_dir, ptrs = check_query_into(
+            flags, self.device, origins, directions, dict(t=t, index=index, normal=normal, point=point, front=front))
+        if stream is not None and (isinstance(stream, bool) or not isinstance(stream, int)):
+            raise TypeError(f"stream must be an integer stream handle or None, not {stream!r}")
+        if self._scene_flat is None:
+            raise RuntimeError("query_into needs a scene: call set_scene first")
+        op = origin.ctypes.data_as(ctypes.POINTER(abi.f64)) if origin is not None else None
+        abi.check(self.lib, self.lib.rt_query_hits_async(self.ctx, n, d_org, op, d_dir, flags,
+                                                         *[ptrs.get(name) for name in QUERY_NAMES], stream))
+        return n
 
     def begin_progressive(self, max_bounces, spp_capacity, scene, camera, tile_range=None, max_bytes=0):
         """Open a ProgressiveSession (rt_progressive_begin) for up to spp_capacity samples per pixel.  The live
