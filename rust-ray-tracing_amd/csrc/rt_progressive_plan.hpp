@@ -1,9 +1,13 @@
 // rt_progressive_plan.hpp — the host arithmetic of a progressive session (rt_progressive_*): the record
 // buffer a session of a given sample capacity needs, and how one extend's sample window [done, spp_total)
-// is dealt into work items, uniformly or with a sample count per pixel.  Pure host C++ (no HIP): the library and
-// the stand-alone sanitizer programs tests/sanitize/progressive_plan_san.cpp and map_plan_san.cpp include it.
+// is dealt into work items, uniformly or with a sample count per pixel, and how a reduction's pixels are grouped
+// by count.  Pure host C++ (no HIP): the library, the stand-alone sanitizer programs
+// tests/sanitize/progressive_plan_san.cpp and map_plan_san.cpp and tests/group_by_count_check.cpp include it.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
+#include <vector>
 
 #include "rt_split_plan.hpp"
 
@@ -145,6 +149,47 @@ inline int progressive_map_plan(uint64_t n_pixels, const uint32_t* done, const u
         }
     }
     return kPlanOk;
+}
+
+// ---- the reductions of a call over per-pixel counts (finish_window_list, a launch per count) ----
+// The pixels of one reduction that share a sample count: list[first .. first + n) of the reduction's index list.
+struct CountClass {
+    uint32_t spp, first, n;
+};
+constexpr size_t kMaxCountClasses = 256;   // distinct counts one reduction may have (a launch each)
+
+// Group the pixels by counts[p] (0: the pixel is left out): the classes in ascending count, and, with list, each
+// class's pixel indices in pixel order.  false: more than kMaxCountClasses distinct counts.
+inline bool group_by_count(const uint32_t* counts, uint32_t n_pix, uint32_t* list, std::vector<CountClass>& cls) {
+    cls.clear();
+    auto find = [&](uint32_t n) {
+        return std::lower_bound(cls.begin(), cls.end(), n, [](const CountClass& k, uint32_t v) { return k.spp < v; });
+    };
+    size_t last = 0;   // the class of the previous pixel: neighbours mostly share a count
+    for (uint32_t p = 0; p < n_pix; ++p) {
+        if (counts[p] == 0u) continue;
+        if (last >= cls.size() || cls[last].spp != counts[p]) {
+            auto it = find(counts[p]);
+            if (it == cls.end() || it->spp != counts[p]) {
+                if (cls.size() == kMaxCountClasses) return false;
+                it = cls.insert(it, CountClass{counts[p], 0u, 0u});
+            }
+            last = (size_t)(it - cls.begin());
+        }
+        ++cls[last].n;
+    }
+    uint32_t at = 0;
+    for (CountClass& k : cls) { k.first = at; at += k.n; }
+    if (!list) return true;
+    for (CountClass& k : cls) k.n = 0u;
+    for (uint32_t p = 0; p < n_pix; ++p) {
+        if (counts[p] == 0u) continue;
+        if (cls[last].spp != counts[p]) last = (size_t)(find(counts[p]) - cls.begin());
+        CountClass& k = cls[last];
+        list[k.first + k.n] = p;
+        ++k.n;
+    }
+    return true;
 }
 
 }  // namespace rt

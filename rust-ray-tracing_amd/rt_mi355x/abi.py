@@ -163,7 +163,7 @@ _lib = None
 # The sources the Makefile hashes into rt_version() ("src=<hash>"), in its order (SRC, then HDR).
 KERNEL_SOURCES = ["rt_kernel.hip", "rt_experiments.hpp", "rt_formats.hpp", "rt_common.hpp", "rt_sweep.hpp",
                   "rt_camera.hpp", "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp",
-                  "rt_progressive_plan.hpp", "rt_guides.hpp", "rt_query.hpp"]
+                  "rt_progressive_plan.hpp", "rt_host.hpp", "rt_launch.hpp", "rt_session.hpp", "rt_guides.hpp", "rt_query.hpp"]
 SOURCE_FILES = [os.path.join(PKG_DIR, "csrc", f) for f in KERNEL_SOURCES] + \
                [os.path.join(os.path.dirname(PKG_DIR), "include", "rt_mi355x.h")]
 

@@ -11,6 +11,7 @@
 #include "rt_sweep.hpp"
 #include "rt_camera.hpp"
 #include "rt_layout.hpp"
+#include "rt_host.hpp"   // the product's device tables and kernel arguments, for the ray probe
 
 using namespace rt;
 
@@ -158,88 +159,45 @@ __global__ void __launch_bounds__(kBlock) k_probe_camera(KParams<T> p, const T* 
     }
 }
 
-// The scene half of KParams<T> over the image's tables, uploaded through dv (rt_kernel.hip's upload_scene and
-// scene_params restated; a table the scene does not have stays unread).  The frame half stays zero.
-template <typename T> KParams<T> probe_params(Dev& dv, const SceneImage& im, bool filter_off) {
-    const SceneTables<T>& t = im.tables<T>();
-    const SceneCounts& n = im.n;
+// The device tables of one scene image at precision T and the kernel arguments over them, both by the product's own
+// steps (rt_host.hpp): upload_scene and scene_params for the scene half (a table the scene does not have stays
+// NULL, unread), cam_table_params and launch_cam_table for the camera tables.  The frame half of p stays zero.
+template <typename T> struct ProbeScene {
+    DeviceScene<T> d;
+    DeviceBuffer ridx, mtiers;
     KParams<T> p;
-    memset(&p, 0, sizeof(p));
-    auto up = [&](const auto& v) { return dv.in(v.data(), v.size()); };
-    p.sph = up(t.sph);
-    p.cen = up(t.cen);
-    p.n_groups = t.k.n_groups;
-    p.fsph = up(t.fsph);
-    p.n_fgroups = n.n_fgroups;
-    p.rsph = up(t.rsph);
-    p.rfsph = up(t.rfsph);
-    p.ftop = up(t.top);
-    p.fsup = up(t.sup);
-    p.rflat = up(t.rflat);
-    p.n_mg = n.n_mg;
-    p.lfsph = up(t.lfs);
-    p.lclb = up(t.lbx[0]);
-    p.lsup = up(t.lbx[1]);
-    p.lmeg = up(t.lbx[2]);
-    p.lgig = up(t.lbx[3]);
-    p.n_gg = n.n_gg;
-    p.mtiers = up(im.mtiers);
-    for (int a = 0; a < 3; ++a) { p.mt_lo[a] = n.mt_lo[a]; p.mt_n[a] = n.mt_n[a]; }
-    p.mt_inv = n.mt_inv;
-    p.l_r2max = t.k.l_r2max;
-    p.l_hir2 = t.k.l_hir2;
-    p.l_isr = t.k.l_isr;
-    p.ridx = up(im.ridx);
-    p.n_top = n.n_top;
-    p.n_xg = n.n_xg;
-    p.n_xs = n.n_xs;
-    p.f_cmax = filter_off ? std::numeric_limits<float>::infinity() : t.k.f_cmax;   // RT_FILTER_OFF (frame_setup)
-    p.f_r2max = t.k.f_r2max;
-    p.f_r2min = t.k.f_r2min;
-    p.f_ir2 = t.k.f_ir2;
-    p.f_hir2 = t.k.f_hir2;
-    p.f_isr = t.k.f_isr;
-    p.mats = up(t.mats);
-    p.n_spheres = n.n_spheres;
-    return p;
-}
-
-// The camera tables of centre c (rt_kernel.hip's ensure_cam_tables restated): build_cam_table, the product's own.
-template <typename T> void probe_cam_tables(Dev& dv, const SceneImage& im, KParams<T>& p, const T* c, bool scalar,
-                                            bool filter_off) {
-    const SceneTables<T>& t = im.tables<T>();
-    const SceneCounts& n = im.n;
-    T* cam = dv.out<T>(t.cam_bytes.cam / sizeof(T));
-    float* camf = dv.out<float>(t.cam_bytes.camf / sizeof(float));
-    T* camx = dv.out<T>(t.cam_bytes.camx / sizeof(T));
-    float* cull = dv.out<float>(t.cam_bytes.cull / sizeof(float));
-    float* cullc = dv.out<float>(t.cam_bytes.cullc / sizeof(float));
-    const double* clus = dv.in(t.clus.data(), t.clus.size());
-    for (int a = 0; a < 3; ++a) p.center[a] = c[a];
-    p.camsph = cam; p.camf = camf; p.camx = camx; p.cull = cull; p.cullc = cullc;
-    p.n_clp = n.n_clp;
-    p.n_supc = n.n_supc;
-    const uint32_t n_slots = (p.n_groups + 1) * kGroup<T>, n_fslots = (p.n_fgroups + 1) * 4;
-    const uint32_t n_thr = std::max(std::max(std::max(n_slots, n_fslots), n.n_cull),
-                                    std::max(n.n_cslots, n.n_clp + n.n_supc));
-    if (!dv.ok()) return;
-    auto build = scalar ? build_cam_table<T, true> : build_cam_table<T, false>;
-    hipLaunchKernelGGL(build, dim3((n_thr + 255) / 256), dim3(256), 0, 0, p.sph, cam, n_slots, camf, n_fslots, c[0], c[1],
-                       c[2], (uint32_t)filter_off, camx, cull, n.n_cull, n.n_spheres, p.ridx, n.n_cslots, clus, cullc,
-                       n.n_clp + n.n_supc);
-    dv.sync();
-}
+    int setup(const SceneImage& im, bool filter_off) {
+        int rc = upload_scene(d, im.tables<T>());
+        if (rc == RT_OK) rc = upload(ridx, im.ridx);
+        if (rc == RT_OK) rc = upload(mtiers, im.mtiers);
+        memset(&p, 0, sizeof(p));
+        scene_params(d, im.n, ridx, mtiers, filter_off, p);
+        return rc;
+    }
+    // The camera tables of centre c, built on the null stream; returns once they are there.
+    int cam_tables(const SceneImage& im, const T* c, bool scalar, bool filter_off) {
+        for (int a = 0; a < 3; ++a) p.center[a] = c[a];
+        cam_table_params(d, im.n, p);
+        const int rc = launch_cam_table(d, im.n, ridx, p.center, scalar, filter_off, 0);
+        if (rc != RT_OK) return rc;
+        return hipDeviceSynchronize() == hipSuccess ? RT_OK : RT_ERR_HIP;
+    }
+};
 
 // mode 0: the live path <T, false, false>, 1: root2 <T, true, false>, 2: scalar <T, false, true>; MEGA as the
-// launchers pick it (n_mg > 0).  centre == nullptr: the general probe.
+// launchers pick it (n_mg > 0).  centre == nullptr: the general probe.  Returns 0, a HIP error of the probe's own
+// calls, or the product's error code (RT_ERR_HIP) where its steps failed.
 template <typename T>
 int probe(const rt_scene* s, int mode, int filter_off, const T* centre, const T* o, const T* d, const uint8_t* active,
           int32_t* idx, T* t, size_t n) {
     if (!s || mode < 0 || mode > 2 || n % kBlock != 0 || n > (1u << 24)) return -1;
     const SceneImage im = build_scene_image(s);
+    ProbeScene<T> ps;
+    int rc = ps.setup(im, filter_off != 0);
+    if (rc == RT_OK && centre) rc = ps.cam_tables(im, centre, mode == 2, filter_off != 0);
+    if (rc != RT_OK) return rc;
+    const KParams<T>& p = ps.p;
     Dev dv;
-    KParams<T> p = probe_params<T>(dv, im, filter_off != 0);
-    if (centre) probe_cam_tables<T>(dv, im, p, centre, mode == 2, filter_off != 0);
     const T* dor = centre ? nullptr : dv.in(o, 3 * n);
     const T* dd = dv.in(d, 3 * n);
     const uint8_t* da = dv.in(active, n);
@@ -360,7 +318,7 @@ int du_philox2x32_10(const uint32_t* ctr, const uint32_t* key, uint32_t* out, si
         const uint32_t* dc = d.in(ctr, 2 * n); const uint32_t* dk = d.in(key, n); uint32_t* o = d.out<uint32_t>(2 * n);
         LAUNCH(k_philox2, dc, dk, o, n); d.back(out, o, 2 * n); });
 }
-// The host's fp32 key fold (rt_kernel.hip launch_t): seed lo ^ fmix32(seed hi), with rt_device.hpp's fmix32.
+// The host's fp32 key fold (rt_launch.hpp frame_params): seed lo ^ fmix32(seed hi), with rt_device.hpp's fmix32.
 uint32_t du_fold_key_f32(uint64_t seed) { return (uint32_t)seed ^ fmix32((uint32_t)(seed >> 32)); }
 
 // sqrt over the `count` bit patterns from `start` (wrapping mod 2^32); count a multiple of 256, and of 2^22 when
