@@ -137,6 +137,9 @@ typedef struct rt_stats {
  * MEGA mean what they mean above, CAMQ is SHARED (the shared-origin path: the camera sweep over the origin's camera
  * tables), MODE, SPLIT, ITEMS and GUIDES are 0. */
 #define RT_KERNEL_QUERY(id) (((id) >> 12) & 1u)
+/* Set: the caller-ray kernel ran, trace_paths_rays<T, W, ROOT2, MEGA> (rt_render_rays_async; rays_validate<T> runs
+ * ahead of it); F64, WAVES, ROOT2 and MEGA mean what they mean above, CAMQ, MODE, SPLIT, ITEMS, GUIDES and QUERY are 0. */
+#define RT_KERNEL_RAYS(id) (((id) >> 13) & 1u)
 
 /* ---- flags ---- */
 #define RT_FLAG_F32 0x1u     /* compute in fp32 (default: fp64, the reference's arithmetic) */
@@ -305,6 +308,63 @@ int rt_render_guides_async(rt_context* ctx, const rt_camera* camera, uint32_t sp
 int rt_query_hits_async(rt_context* ctx, uint64_t n_rays, const void* d_origins, const double* origin,
                         const void* d_directions, uint32_t flags, void* d_t, void* d_index, void* d_normal,
                         void* d_point, void* d_front, void* stream);
+/* ---- rendering caller-supplied primary rays: any camera model, full paths ----
+ * rt_render_async with the primary rays taken from the caller's arrays instead of Camera::get_ray: an orthographic
+ * view, a fisheye, a 360 degree panorama (rt_camera_rays below makes their rays) or the rays of the caller's own
+ * tensors, path-traced to an image.  T is float under RT_FLAG_F32 and double otherwise; R = rays_per_pixel, 1 <= R <= spp.
+ * Definition:
+ *   pixel p   in [0, n_pixels) is the live path's pixel (render_vectorized2 -> trace_vectorized2, quirks Q1-Q3 as
+ *             rt_render_async has them): spp samples in chunks of 4.
+ *   sample s  starts as ray p R + (s mod R) of the caller's arrays, taken as given: directions are NOT normalised, and
+ *             quirk Q2's sky reads the primary direction's y as supplied.
+ *   draws     every later draw is the render's: stream 2, counter (s, pix, bounce) with pix = pixel_base + p.  Streams
+ *             0 and 1 (the camera's jitter and defocus disk) are never drawn.  pixel_base + n_pixels above 2^32 is
+ *             RT_ERR_INVALID; shards of one frame pass their first pixel as pixel_base to keep their streams apart.
+ * Rays: d_directions is device [n_pixels R][3] of T; the origins come in exactly the two forms of rt_query_hits_async
+ * (per ray: d_origins device [n_pixels R][3] of T; shared: 3 HOST doubles rounded as (T)origin[i]).  Both forms give
+ * identical values, and both run every bounce through the general sweep (no camera batches over a shared origin).
+ * Precondition, per ray: the query's (finite components, |d|^2 in T within [1e-6, 1e6], the bounds included).  A pixel
+ * with an invalid ray among its R is not traced: its linear output is NaN x 3, its rgb8 is 0, 0, 0, it raises no
+ * RT_ERR_RANGE and the other pixels do not depend on it.  (A fisheye pixel outside the image circle is such a pixel.)
+ * Outputs: rt_render_async's, d_rgb8 [n_pixels][3] u8 and d_linear [n_pixels][3] double, device pointers, one of them
+ * may be NULL.  RT_ERR_RANGE is reported at rt_context_collect as for a render.
+ * flags: RT_FLAG_F32 and RT_FLAG_ROOT2.  Any RT_FLAG_MODE_* is RT_ERR_UNSUPPORTED; unknown bits are RT_ERR_INVALID.
+ * n_pixels == 0: RT_OK, nothing is enqueued.  RT_ERR_UNSUPPORTED: spp > 2^20, fp32 with max_bounces >
+ * RT_MAX_BOUNCES_F32, n_pixels > 0x7FFFFFFF.  RT_ERR_INVALID, checked before any HIP call: ctx or d_directions NULL,
+ * both or neither origin form, both outputs NULL, spp == 0, R == 0 or R > spp, no scene set.
+ * Asynchronous on `stream` under rt_render_async's cross-stream rule.  Allowed while a progressive session is open;
+ * touches neither its records nor its counts.
+ * rt_context_collect after it: pixels = n_pixels, samples = valid pixels x spp, ray_segments and bounce_iters as a
+ * render counts them (over the valid pixels), RT_KERNEL_RAYS(kernel_id) is set.
+ * Out of scope: sample-parallel splitting, progressive sessions and guides over caller rays, the other semantics
+ * modes, sorting or binning incoherent rays. */
+int rt_render_rays_async(rt_context* ctx, uint64_t n_pixels, uint32_t spp, uint32_t rays_per_pixel,
+                         const void* d_origins, const double* origin, const void* d_directions,
+                         uint32_t max_bounces, uint64_t seed, uint32_t pixel_base, uint32_t flags,
+                         void* d_rgb8, void* d_linear, void* stream);
+/* Host only, needs no GPU: the primary rays of three camera models the reference lacks, for rt_render_rays_async
+ * (rays_per_pixel = grid^2) or rt_query_hits_async.  origins and directions are HOST arrays
+ * [image_width image_height grid^2][3] of T (float under RT_FLAG_F32, else double), pixels row-major from the top
+ * left, and within a pixel ray r = j grid + i goes through the sub-pixel position ((i + 0.5) / grid, (j + 0.5) / grid).
+ * The frame is Camera::new's (ray_tracing.rs:34-37): dir = unit(look_at - center), w = -dir, u = unit(up x w) (right),
+ * v = w x u (up).  Everything is computed in double; directions are unit in double; values are rounded to T last.
+ * A fisheye pixel outside the image circle gets the direction 0, 0, 0: an invalid ray, so rt_render_rays_async
+ * renders that pixel black (linear NaN) and rt_query_hits_async reports RT_QUERY_INVALID.
+ * RT_ERR_INVALID: a NULL argument, an empty image, grid == 0, an unknown model, a flag other than RT_FLAG_F32, a frame
+ * that cannot be built (non-finite, look_at == center, up along the view axis), a fisheye angle_deg outside
+ * (0, 360], an orthographic extent that is not a positive number.  RT_ERR_UNSUPPORTED: more than 0x7FFFFFFF pixels,
+ * grid > 1024. */
+#define RT_PROJ_ORTHOGRAPHIC 0u   /* parallel rays along the view axis; origins on a plane through center,
+                                     `extent` world units high, width by the aspect ratio */
+#define RT_PROJ_EQUIRECT 1u       /* 360 x 180 degrees: longitude over columns, latitude over rows, one origin */
+#define RT_PROJ_FISHEYE 2u        /* equidistant: angle from the axis = r * angle_deg / 2, r = distance from the
+                                     image centre in units of half the shorter side; r > 1: a zero direction */
+typedef struct rt_projection {
+    uint32_t model, image_width, image_height;
+    double center[3], look_at[3], up[3];
+    double angle_deg, extent;   /* fisheye: the full field of view in degrees; orthographic: the view's height */
+} rt_projection;
+int rt_camera_rays(const rt_projection* proj, uint32_t grid, uint32_t flags, void* origins, void* directions);
 /* The plan rt_render_split_async makes for samples_per_item = 0; host only, needs no GPU.
  * resident_waves: the waves the split kernels keep resident (CUs x 4 SIMDs x 5 waves in fp32, x 4 in fp64).
  * Returns the samples per item (a multiple of 128, or spp when the plan is one item per pixel) and the

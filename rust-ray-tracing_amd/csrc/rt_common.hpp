@@ -156,6 +156,17 @@ template <typename T> struct LParams {
     const uint32_t* list;
 };
 
+// Arguments of the caller-ray kernel (trace_paths_rays, rt_rays.hpp; rt_render_rays_async): KParams first, at the
+// same kernarg offsets (n_items: the pixels), then the caller's rays.  Pixel p's sample s starts as ray
+// p R + s % R; its RNG pixel is pixel_base + p.
+template <typename T> struct RParams {
+    KParams<T> k;
+    const T* origins;          // [n_items R][3]; NULL: one shared origin, k.center
+    const T* directions;       // [n_items R][3], not normalised
+    uint64_t* skip;            // bit p % 64 of word p / 64: pixel p has an invalid ray and is not traced (rays_validate)
+    uint32_t R, pixel_base;
+};
+
 constexpr int kSegShards = 256;
 constexpr uint32_t kFlagPinholeInternal = 0x80000000u;   // set by the host: defocus vectors are +-0
 constexpr int kWavesF32 = 6;   // default min-waves-per-SIMD targets (measured sweep);
@@ -237,6 +248,12 @@ template <typename T> __device__ __forceinline__ cptr<IParams<T>> cold_items_arg
 }
 template <typename T> __device__ __forceinline__ cptr<LParams<T>> cold_list_args() {
     cptr<LParams<T>> k = (cptr<LParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return k;
+}
+// ... and the caller-ray kernel's.
+template <typename T> __device__ __forceinline__ cptr<RParams<T>> cold_rays_args() {
+    cptr<RParams<T>> k = (cptr<RParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));
     return k;
 }

@@ -31,7 +31,8 @@
 // layout and device code share; no HIP), rt_common.hpp (kernel arguments, scalar-load pipelines),
 // rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (replay + reduction),
 // rt_trace.hpp + rt_trace_body.hpp (the persistent kernel), rt_guides.hpp (guide buffers: first hits only),
-// rt_query.hpp (ray queries: the closest hit of the caller's rays);
+// rt_query.hpp (ray queries: the closest hit of the caller's rays), rt_rays.hpp (full paths for the caller's
+// primary rays); rt_projection.hpp (host only: the rays of camera models the reference lacks);
 // host only, without HIP: rt_layout.hpp (the scene image: every device table of a scene, build_scene_image),
 // rt_split_plan.hpp (the sample-parallel plan), rt_progressive_plan.hpp (a progressive session's record buffer,
 // sample windows and count classes);
@@ -40,10 +41,11 @@
 // launch_cam_table; it knows no context, and the test-only device library builds its arguments with it),
 // rt_launch.hpp (what a context's launches share, kernel selection and kernel_id, the launch steps frame_params,
 // ensure_cam_tables, frame_setup, plan_grid, and the launchers launch_plain, launch_split, launch_window,
-// launch_guides, launch_query), rt_session.hpp (a progressive session: its state, launch_items and launch_classes
+// launch_guides, launch_query, launch_rays), rt_session.hpp (a progressive session: its state, launch_items and launch_classes
 // for per-pixel counts, extend_uniform, run_map, snapshot_run and the steps of refine_step).  This file holds the
 // C ABI: rt_context, the entry points (their argument checks, then one call) and the small device helpers.
 #include "rt_session.hpp"
+#include "rt_projection.hpp"
 
 #include <chrono>
 
@@ -106,7 +108,7 @@ static void free_scene(rt_context* c) {
 // Everything a context made, and the context: what init_context did not get to is still NULL.
 static void free_context(rt_context* c) {
     free_scene(c);
-    c->segs.reset(); c->err.reset(); c->counter.reset(); c->scratch.reset(); c->records.reset();
+    c->segs.reset(); c->err.reset(); c->counter.reset(); c->scratch.reset(); c->records.reset(); c->rayskip.reset();
     if (c->ev_first) (void)hipEventDestroy(c->ev_first);
     if (c->ev_last) (void)hipEventDestroy(c->ev_last);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -314,6 +316,48 @@ extern "C" int rt_query_hits_async(rt_context* c, uint64_t n_rays, const void* d
     rc = with_precision((flags & RT_FLAG_F32) != 0, [&](auto t) { return launch_query<decltype(t)>(c, a, st); });
     if (rc != RT_OK) return rc;
     return end_launch(c, st, n_rays, 0u);   // samples: the valid rays, counted on the device (kQuerySlot)
+}
+
+extern "C" int rt_render_rays_async(rt_context* c, uint64_t n_pixels, uint32_t spp, uint32_t rays_per_pixel,
+                                    const void* d_origins, const double* origin, const void* d_directions,
+                                    uint32_t max_bounces, uint64_t seed, uint32_t pixel_base, uint32_t flags,
+                                    void* d_rgb8, void* d_linear, void* stream) {
+    const std::string who = "rt_render_rays_async";
+    if (!c || !d_directions) return fail(RT_ERR_INVALID, who + ": NULL argument (ctx or d_directions)");
+    if ((d_origins != nullptr) == (origin != nullptr))
+        return fail(RT_ERR_INVALID, who + ": exactly one of d_origins (per ray) and origin (shared) must be given");
+    if (!d_rgb8 && !d_linear) return fail(RT_ERR_INVALID, who + ": both outputs are NULL");
+    if (spp == 0) return fail(RT_ERR_INVALID, who + ": spp == 0 (the reference panics: 0/0 in to_u8_array)");
+    if (rays_per_pixel == 0 || rays_per_pixel > spp)
+        return fail(RT_ERR_INVALID, who + ": rays_per_pixel outside 1..spp");
+    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
+    if (flags & ~(RT_FLAG_F32 | RT_FLAG_ROOT2))
+        return fail(RT_ERR_UNSUPPORTED, who + ": the live path only (RT_FLAG_F32, RT_FLAG_ROOT2; no RT_FLAG_MODE_*)");
+    if (spp > (1u << 20)) return fail(RT_ERR_UNSUPPORTED, who + ": spp > 2^20");
+    if ((flags & RT_FLAG_F32) && max_bounces > RT_MAX_BOUNCES_F32)
+        return fail(RT_ERR_UNSUPPORTED, who + ": fp32 with max_bounces > RT_MAX_BOUNCES_F32 (3839)");
+    if (n_pixels > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many pixels in one call");
+    if ((uint64_t)pixel_base + n_pixels > (1ull << 32))
+        return fail(RT_ERR_INVALID, who + ": pixel_base + n_pixels above 2^32 (the RNG's pixel is 32 bits)");
+    if (!c->has_scene) return fail(RT_ERR_INVALID, who + ": no scene set (rt_context_set_scene first)");
+    if (n_pixels == 0) return RT_OK;
+    const RayArgs a{n_pixels, spp, rays_per_pixel, d_origins, origin, d_directions, max_bounces, seed, pixel_base, flags,
+                    d_rgb8, d_linear};
+    hipStream_t st = (hipStream_t)stream;
+    int rc = begin_launch(c, st);
+    if (rc != RT_OK) return rc;
+    rc = with_precision((flags & RT_FLAG_F32) != 0, [&](auto t) { return launch_rays<decltype(t)>(c, a, st); });
+    if (rc != RT_OK) return rc;
+    return end_launch(c, st, n_pixels, 0u);   // samples: valid pixels x spp, counted on the device (rays_validate)
+}
+
+extern "C" int rt_camera_rays(const rt_projection* proj, uint32_t grid, uint32_t flags, void* origins, void* directions) {
+    const int rc = camera_rays(proj, grid, flags, origins, directions);
+    if (rc != kProjOk)
+        return fail(rc, "rt_camera_rays: a NULL argument, an empty image, grid == 0, an unknown model or flag, a frame that "
+                        "cannot be built (look_at == center, up along the view axis), angle_deg outside (0, 360] or "
+                        "extent <= 0 (invalid); more than 2^31 - 1 pixels or grid > 1024 (unsupported)");
+    return RT_OK;
 }
 
 extern "C" int rt_split_plan(uint64_t n_pixels, uint32_t spp, uint32_t resident_waves, uint32_t* samples_per_item,
@@ -542,7 +586,7 @@ extern "C" int rt_context_collect(rt_context* c, void* stream, rt_stats* out) {
         slots += segs[(size_t)i * kSegStride + 1];
         iters += segs[(size_t)i * kSegStride + 2];
         dsky += segs[(size_t)i * kSegStride + kDirectSkySlot];
-        qrays += segs[(size_t)i * kSegStride + kQuerySlot];   // the valid rays of the queries
+        qrays += segs[(size_t)i * kSegStride + kQuerySlot];   // the valid rays of the queries, the samples of the ray renders' valid pixels
         for (uint32_t j = 0; j < kNWork; ++j) work[j] += segs[(size_t)i * kSegStride + kWorkSlot + j];
     }
     if (out) {

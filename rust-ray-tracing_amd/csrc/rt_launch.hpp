@@ -1,11 +1,12 @@
 // rt_launch.hpp — the launches of the C ABI, host only: what the launches of a context share (LaunchContext),
 // the kernel selection and rt_stats.kernel_id, the steps of a launch (context_params, frame_params,
 // ensure_cam_tables, frame_setup, plan_grid) and the launchers (launch_plain, launch_split, launch_window,
-// launch_guides, launch_query), between begin_launch and end_launch.
+// launch_guides, launch_query, launch_rays), between begin_launch and end_launch.
 #pragma once
 #include "rt_trace.hpp"
 #include "rt_guides.hpp"
 #include "rt_query.hpp"
+#include "rt_rays.hpp"
 #include "rt_host.hpp"
 #include "rt_split_plan.hpp"
 #include "rt_progressive_plan.hpp"
@@ -31,6 +32,7 @@ struct LaunchContext {
     DeviceBuffer counter;   // persistent-kernel claim-stream counters (zeroed before each launch)
     DeviceBuffer scratch;   // per-wave ray state (grown on demand)
     DeviceBuffer records;   // the sample-parallel path's record buffer (grown on demand)
+    DeviceBuffer rayskip;   // rt_render_rays_async: one bit per pixel, set where a ray is invalid (grown on demand)
     int n_cu = 0;
     uint64_t samples = 0, pixels = 0;
     hipStream_t last_stream = nullptr;   // stream of the previous render (they share scratch and tables)
@@ -44,6 +46,7 @@ constexpr uint32_t kKernelSplitBit = 1u << 9;     // the sample-parallel kernels
 constexpr uint32_t kKernelItemsBit = 1u << 10;    // with kKernelSplitBit: a session's item-table kernel
 constexpr uint32_t kKernelGuidesBit = 1u << 11;   // guide_pixels
 constexpr uint32_t kKernelQueryBit = 1u << 12;    // query_rays (its SHARED takes the camera-batch bit)
+constexpr uint32_t kKernelRaysBit = 1u << 13;     // trace_paths_rays
 template <typename T>
 constexpr uint32_t kernel_id(int W, bool root2, int mode, bool camq, bool mega, uint32_t family) {
     return 0x8000u | (sizeof(T) == 8 ? 1u : 0u) | ((uint32_t)W << 1) | (root2 ? kKernelRoot2Bit : 0u) |
@@ -128,6 +131,11 @@ static void (*pick_guides(bool camq, bool mega))(GParams<T>) {
 template <typename T>
 static void (*pick_query(bool root2, bool shared, bool mega))(QParams<T>) {
     return with_bools([](auto r2, auto sh, auto mg) { return query_rays<T, r2.value, sh.value, mg.value>; }, root2, shared, mega);
+}
+// The caller-ray kernel (rt_render_rays_async): trace_paths_rays<T, W, ROOT2, MEGA> at the precision's default W.
+template <typename T>
+static void (*pick_rays(bool root2, bool mega))(RParams<T>) {
+    return with_bools([](auto r2, auto mg) { return trace_paths_rays<T, kWavesRays<T>, r2.value, mg.value>; }, root2, mega);
 }
 constexpr uint64_t kScratchBudget = 24ull << 30;   // scratch (and record buffer) bytes a launch may ask for
 
@@ -402,6 +410,62 @@ static int launch_query(LaunchContext* c, const QueryArgs& a, hipStream_t st) {
     qp.point = (T*)a.point;
     qp.front = (uint8_t*)a.front;
     hipLaunchKernelGGL(qfn, dim3((uint32_t)nblocks), dim3(256), 0, st, qp);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// What rt_render_rays_async asks for: the rays (R per pixel; origins as a query's) and a render's outputs.
+struct RayArgs {
+    uint64_t n_pixels;
+    uint32_t spp, R;
+    const void* origins;
+    const double* origin;
+    const void* directions;
+    uint32_t depth;
+    uint64_t seed;
+    uint32_t pixel_base, flags;
+    void *rgb, *lin;
+};
+
+// rays_validate, then trace_paths_rays: one work item per pixel, every sample of it, as launch_plain has them.  The
+// frame is a render's of one row of n_pixels columns under a camera that has only a centre (the shared origin,
+// rounded as a camera centre is; unused with per-ray origins): frame_params sets the sample counts, the RNG key and
+// the record layout.  No camera tables: every bounce goes through the general sweep.
+template <typename T>
+static int launch_rays(LaunchContext* c, const RayArgs& a, hipStream_t st) {
+    rt_camera cam;
+    memset(&cam, 0, sizeof(cam));
+    cam.image_width = cam.image_height = 1u;
+    if (a.origin) for (int i = 0; i < 3; ++i) cam.center[i] = a.origin[i];
+    const FrameArgs fa{&cam, a.depth, a.spp, a.seed, a.flags, rt_tile_range{0u, 1u, 1u, 0u, (uint32_t)a.n_pixels}, a.rgb, a.lin};
+    KParams<T> p;
+    context_params(c, filter_off_env(), p);
+    frame_params(fa, p);
+    const bool root2 = (a.flags & RT_FLAG_ROOT2) != 0u, mega = p.n_mg > 0;
+    void (*const rfn)(RParams<T>) = pick_rays<T>(root2, mega);
+    constexpr int W = kWavesRays<T>;
+    const uint32_t id = kernel_id<T>(W, root2, kModeV2, false, mega, kKernelRaysBit);
+    uint64_t nblocks = 0;
+    int rc = plan_grid(c, (const void*)rfn, W, id, p.n_items, a.spp, nblocks, p.blk_g);
+    if (rc != RT_OK) return rc;
+    p.scratch_stride = (size_t)p.vbytes + (size_t)kSlots * p.sbytes;
+    const uint64_t max_blocks = kScratchBudget / (4 * p.scratch_stride);   // as launch_plain keeps its scratch
+    if (nblocks > max_blocks) nblocks = max_blocks > 0 ? max_blocks : 1;
+    if ((rc = ensure_bytes(c->scratch, p.scratch_stride * nblocks * 4, st)) != RT_OK) return rc;
+    p.scratch = (char*)c->scratch.p;
+    if ((rc = ensure_bytes(c->rayskip, (size_t)((a.n_pixels + 63u) / 64u) * sizeof(uint64_t), st)) != RT_OK) return rc;
+    RParams<T> rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.k = p;
+    rp.origins = (const T*)a.origins;
+    rp.directions = (const T*)a.directions;
+    rp.skip = (uint64_t*)c->rayskip.p;
+    rp.R = a.R;
+    rp.pixel_base = a.pixel_base;
+    if ((rc = zero_claim_counters(c, st)) != RT_OK) return rc;
+    hipLaunchKernelGGL(rays_validate<T>, dim3((uint32_t)((a.n_pixels + 255u) / 256u)), dim3(256), 0, st, rp);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(rfn, dim3((uint32_t)nblocks), dim3(256), 0, st, rp);
     HIPCHK(hipGetLastError());
     return RT_OK;
 }

@@ -90,6 +90,7 @@ template <typename T, bool B> constexpr bool kSplitKernel = B;
 template <typename T, int W, bool ROOT2, int MODE = kModeV2, bool CAMQ = false, bool MEGA = false>
 __global__ __launch_bounds__(256, W) void trace_paths(KParams<T> p) {
     constexpr bool SPLIT = kSplitKernel<T, false>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, false>;
+    constexpr bool RAYS = kSplitKernel<T, false>;
 #include "rt_trace_body.hpp"
 }
 
@@ -98,6 +99,7 @@ __global__ __launch_bounds__(256, W) void trace_paths(KParams<T> p) {
 template <typename T, int W, bool CAMQ, bool MEGA>
 __global__ __launch_bounds__(256, W) void trace_paths_split(SParams<T> sp) {
     constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, false>, ROOT2 = false;
+    constexpr bool RAYS = kSplitKernel<T, false>;
     constexpr int MODE = kModeV2;
     const KParams<T>& p = sp.k;
 #include "rt_trace_body.hpp"
@@ -109,6 +111,7 @@ __global__ __launch_bounds__(256, W) void trace_paths_split(SParams<T> sp) {
 template <typename T, int W, bool CAMQ, bool MEGA>
 __global__ __launch_bounds__(256, W) void trace_paths_window(WParams<T> wp) {
     constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, true>, ITEMS = kSplitKernel<T, false>, ROOT2 = false;
+    constexpr bool RAYS = kSplitKernel<T, false>;
     constexpr int MODE = kModeV2;
     const KParams<T>& p = wp.s.k;
 #include "rt_trace_body.hpp"
@@ -121,6 +124,7 @@ __global__ __launch_bounds__(256, W) void trace_paths_window(WParams<T> wp) {
 template <typename T, int W, bool CAMQ, bool MEGA>
 __global__ __launch_bounds__(256, W) void trace_paths_items(IParams<T> ip) {
     constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, true>, ROOT2 = false;
+    constexpr bool RAYS = kSplitKernel<T, false>;
     constexpr int MODE = kModeV2;
     const KParams<T>& p = ip.w.s.k;
 #include "rt_trace_body.hpp"

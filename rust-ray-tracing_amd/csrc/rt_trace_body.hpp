@@ -1,10 +1,12 @@
 // rt_trace_body.hpp -- the statements of the persistent path-regeneration kernel, included as the body of
 // trace_paths and of trace_paths_split (rt_trace.hpp; not a header on its own).  In scope: T, W, ROOT2, MODE,
 // CAMQ, MEGA, SPLIT, WIN (SPLIT only: the items tile a sample window, WParams<T>), ITEMS (SPLIT only: the items
-// are read from a table, IParams<T>) and the kernel arguments p (KParams<T>).
+// are read from a table, IParams<T>), RAYS (trace_paths_rays, rt_rays.hpp: the primary rays are the caller's,
+// RParams<T>) and the kernel arguments p (KParams<T>).
     constexpr bool SC = MODE == kModeScalar;
     static_assert(!SPLIT || (MODE == kModeV2 && !ROOT2), "the sample-parallel kernels cover the live path only");
     static_assert(!ITEMS || (SPLIT && !WIN), "an item table replaces the window's decode");
+    static_assert(!RAYS || (!SPLIT && !CAMQ && MODE == kModeV2), "caller rays: the live path, one item per pixel, no camera batches");
     // fp64 at 5+ waves per SIMD: a 64-entry queue (half the LDS), so the parked ray fits in 32 KB per
     // workgroup
     constexpr bool kF64Park = sizeof(T) == 8 && W >= 5;
@@ -196,10 +198,20 @@
                     }
                     item = px;
                 }
-                const uint32_t ri = item / q.col_count, ci = item % q.col_count;
-                cur_row = q.row_begin + ri * q.row_step;
-                cur_col = q.col_begin + ci;
-                cur_pix = cur_row * q.W + cur_col;
+                if constexpr (RAYS) {   // the caller's pixel: no camera, no image coordinates
+                    const auto& rq = *cold_rays_args<T>();
+                    cur_row = 0u;
+                    cur_col = 0u;
+                    cur_pix = rq.pixel_base + item;
+                    // a pixel with an invalid ray is not traced: rays_validate wrote its outputs; its slot stays free
+                    const cptr<uint64_t> skip = (cptr<uint64_t>)__builtin_assume_aligned(rq.skip, 8);
+                    if ((skip[item >> 6] >> (item & 63u)) & 1ull) continue;
+                } else {
+                    const uint32_t ri = item / q.col_count, ci = item % q.col_count;
+                    cur_row = q.row_begin + ri * q.row_step;
+                    cur_col = q.col_begin + ci;
+                    cur_pix = cur_row * q.W + cur_col;
+                }
                 if constexpr (kDirectSky) {
                     if (cold_args<T>()->depth > 1u) {
                         // the pixel's camera candidate list now, not at its slot's first batch: an empty
@@ -421,7 +433,25 @@
         if (fresh || scat) {
             const uint32_t ssv = ss_get();
             const uint32_t pix = (!CAMQ && fresh) ? npix : s_slotpix[wave][slot_of(ssv)];
-            next_ray<T, SC>(CAMQ ? false : fresh, fcol, frow, pix, sid_of(ssv), k, hit_i, hit_t, o, d, c);
+            if constexpr (RAYS) {
+                if (fresh) {   // the caller's ray p R + s % R, as given: not normalised, colour 1
+                    const auto& rq = *cold_rays_args<T>();
+                    const size_t ray = (size_t)(pix - rq.pixel_base) * rq.R + sid_of(ssv) % rq.R;
+                    const T* dp = rq.directions + 3 * ray;
+                    d = mk(dp[0], dp[1], dp[2]);
+                    if (rq.origins != nullptr) {
+                        const T* op = rq.origins + 3 * ray;
+                        o = mk(op[0], op[1], op[2]);
+                    } else {
+                        o = mk(rq.k.center[0], rq.k.center[1], rq.k.center[2]);
+                    }
+                    c = mk(T(1.0), T(1.0), T(1.0));
+                } else {
+                    next_ray<T, SC>(false, fcol, frow, pix, sid_of(ssv), k, hit_i, hit_t, o, d, c);
+                }
+            } else {
+                next_ray<T, SC>(CAMQ ? false : fresh, fcol, frow, pix, sid_of(ssv), k, hit_i, hit_t, o, d, c);
+            }
         }
         if constexpr (kPark) park(o, d);
         if constexpr (kParkC) park_c(c);

@@ -4,7 +4,8 @@
 //             [--seed 0x5EED0001] [--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar]
 //             [--out output.png|.ppm] [--block-size B] [--sample-parallel] [--progressive n1,n2,...]
 //             [--adaptive TOL --spp-min N [--count-map counts.png|.ppm] [--device-plan]] [--guides] [--dump-scene]
-//             [--pick COL,ROW]...
+//             [--pick COL,ROW]... [--look-from X,Y,Z] [--look-at X,Y,Z] [--up X,Y,Z]
+//             [--projection ortho|equirect|fisheye [--proj-angle DEG] [--proj-extent E] [--aa G]]
 //
 // --mode picks which of the reference's renderers is reproduced (include/rt_mi355x.h): the live
 // render_vectorized2 (default), render_vectorized, or the scalar render.
@@ -34,6 +35,15 @@
 // the numbers with enough digits to round-trip.  --mode vectorized2 only, and not with an option that says how or
 // where an image is rendered (--out, --block-size, --sample-parallel, --progressive, --adaptive, --guides): each is
 // refused.  --root2 is what a pick does anyway and is accepted; --spp, --bounces and --seed have no effect.
+//
+// --projection ortho|equirect|fisheye renders the frame through a camera model the reference lacks: the rays come
+// from rt_camera_rays (orthographic: parallel rays over a plane --proj-extent world units high, default 10; equirect:
+// a 360 x 180 degree panorama; fisheye: equidistant, --proj-angle degrees across the shorter side, default 180, black
+// outside the image circle), G x G of them per pixel on a regular sub-pixel grid (--aa G, default 1; needs --spp >=
+// G^2), are uploaded and path-traced in full by rt_render_rays_async; --out is written as ever.  --f32 and --root2
+// are allowed.  Refused, each with a message, together with --mode, --block-size, --sample-parallel, --progressive,
+// --adaptive, --guides or --pick.  --look-from, --look-at and --up (each X,Y,Z) place the camera, the perspective
+// one too; their defaults are main.rs's.
 //
 // Defaults are main.rs's hard-coded values (scene.toml in the working directory, 3840x2160, 50
 // bounces, 100 spp, camera from (16,2,18.5) looking at the origin, vfov 30, focal 10, no defocus,
@@ -103,6 +113,23 @@ int main(int argc, char** argv) {
     bool progressive = false, adaptive = false, device_plan = false;
     double tolerance = 0.0;
     uint32_t spp_min = 0;
+    std::string projection;   // --projection: "", ortho, equirect or fisheye
+    double proj_angle = 180.0, proj_extent = 10.0;
+    uint32_t aa = 1;
+    bool proj_opts = false, mode_given = false;
+    double look_from[3] = {16.0, 2.0, 18.5}, look_at[3] = {0.0, 0.0, 0.0}, up[3] = {0.0, 1.0, 0.0};   // main.rs:51-58
+    auto vec3_arg = [](const std::string& name, const std::string& v, double out[3]) {
+        std::stringstream vs(v);
+        std::string tok;
+        int k = 0;
+        while (std::getline(vs, tok, ',')) {
+            char* end = nullptr;
+            const double x = std::strtod(tok.c_str(), &end);
+            if (tok.empty() || *end != '\0' || k == 3) { k = -1; break; }
+            out[k++] = x;
+        }
+        if (k != 3 || v.back() == ',') { std::fprintf(stderr, "%s: '%s' is not X,Y,Z\n", name.c_str(), v.c_str()); std::exit(2); }
+    };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -124,7 +151,15 @@ int main(int argc, char** argv) {
             else if (m == "vectorized3") flags |= RT_FLAG_MODE_VECTORIZED3;
             else if (m == "scalar") flags |= RT_FLAG_MODE_SCALAR;
             else if (m != "vectorized2") { std::fprintf(stderr, "unknown mode %s\n", m.c_str()); return 2; }
+            mode_given = true;
         }
+        else if (a == "--look-from") vec3_arg(a, next(), look_from);
+        else if (a == "--look-at") vec3_arg(a, next(), look_at);
+        else if (a == "--up") vec3_arg(a, next(), up);
+        else if (a == "--projection") projection = next();
+        else if (a == "--proj-angle") { proj_angle = std::stod(next()); proj_opts = true; }
+        else if (a == "--proj-extent") { proj_extent = std::stod(next()); proj_opts = true; }
+        else if (a == "--aa") { aa = (uint32_t)std::stoul(next()); proj_opts = true; }
         else if (a == "--out") { out = next(); out_given = true; }
         else if (a == "--block-size") block_size = (uint32_t)std::stoul(next());
         else if (a == "--sample-parallel") sample_parallel = true;
@@ -151,7 +186,8 @@ int main(int argc, char** argv) {
             std::puts("rt-render [--scene scene.toml] [--width W] [--height H] [--spp S] [--bounces B] [--seed N] "
                       "[--f32] [--root2] [--mode vectorized2|vectorized|vectorized3|scalar] [--out output.png] [--block-size B] "
                       "[--sample-parallel] [--progressive n1,n2,...] [--adaptive TOL --spp-min N [--count-map PATH] "
-                      "[--device-plan]] [--guides] [--dump-scene] [--pick COL,ROW]...");
+                      "[--device-plan]] [--guides] [--dump-scene] [--pick COL,ROW]... [--look-from X,Y,Z] [--look-at X,Y,Z] "
+                      "[--up X,Y,Z] [--projection ortho|equirect|fisheye [--proj-angle DEG] [--proj-extent E] [--aa G]]");
             return 0;
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -223,6 +259,31 @@ int main(int argc, char** argv) {
                 return bad("(" + std::to_string(p.first) + ", " + std::to_string(p.second) + ") is outside the " +
                            std::to_string(width) + " x " + std::to_string(height) + " frame");
     }
+    uint32_t proj_model = 0;
+    if (!projection.empty()) {
+        auto bad = [](const std::string& why) {
+            std::fprintf(stderr, "--projection: %s\n", why.c_str());
+            return 2;
+        };
+        if (projection == "ortho") proj_model = RT_PROJ_ORTHOGRAPHIC;
+        else if (projection == "equirect") proj_model = RT_PROJ_EQUIRECT;
+        else if (projection == "fisheye") proj_model = RT_PROJ_FISHEYE;
+        else return bad("unknown projection '" + projection + "' (ortho, equirect or fisheye)");
+        if (mode_given) return bad("not with --mode: caller rays are path-traced on the live path only");
+        if (block_size != 0) return bad("not with --block-size: the frame's rays are rendered in one launch");
+        if (sample_parallel) return bad("not with --sample-parallel: caller rays have no sample-parallel kernels");
+        if (progressive) return bad("not with --progressive: a session traces the perspective camera's rays");
+        if (adaptive) return bad("not with --adaptive: a session traces the perspective camera's rays");
+        if (guides) return bad("not with --guides: the guide buffers are the perspective camera's first hits");
+        if (!picks.empty()) return bad("not with --pick: a pick goes through the perspective camera's pixel centres");
+        if (aa == 0 || aa > 1024) return bad("--aa must be between 1 and 1024");
+        if ((uint64_t)aa * aa > spp)
+            return bad("--aa " + std::to_string(aa) + " needs --spp >= " + std::to_string((uint64_t)aa * aa) +
+                       " (one sample per ray of the pixel's grid at least)");
+    } else if (proj_opts) {
+        std::fprintf(stderr, "--proj-angle, --proj-extent and --aa go with --projection\n");
+        return 2;
+    }
     try {
         std::ifstream in(scene_path, std::ios::binary);   // main.rs:31-34
         if (!in) throw Panic("Can't read scene from file " + scene_path);
@@ -236,8 +297,9 @@ int main(int argc, char** argv) {
         }
         if (dump) { dump_scene(scene); return 0; }
 
-        const double from[3] = {16.0, 2.0, 18.5};   // main.rs:51-58
-        Camera camera(width, height, 10.0, 30.0, Vec3{16.0, 2.0, 18.5}, Vec3{0, 0, 0}, Vec3{0, 1, 0}, 0.0);
+        const double* from = look_from;   // main.rs:51-58 unless --look-from, --look-at or --up say otherwise
+        Camera camera(width, height, 10.0, 30.0, Vec3{look_from[0], look_from[1], look_from[2]},
+                      Vec3{look_at[0], look_at[1], look_at[2]}, Vec3{up[0], up[1], up[2]}, 0.0);
         const double vh = std::tan((30.0 * (3.141592653589793 / 180.0)) / 2.0) * 10.0 * 2.0;   // ray_tracing.rs:29
         std::printf("Parameters:\n");                                                          // ray_tracing.rs:46-50
         std::printf("\tCamera Center:            %s\n", rs3(from).c_str());
@@ -283,7 +345,15 @@ int main(int argc, char** argv) {
                         (unsigned long long)traced);
             std::fflush(stdout);
         };
-        auto [image, stat] = adaptive ? renderer.render_adaptive(bounces, spp_min, spp, tolerance, scene, camera,
+        rt_projection proj{};
+        proj.model = proj_model;
+        proj.image_width = width;
+        proj.image_height = height;
+        for (int k = 0; k < 3; ++k) { proj.center[k] = look_from[k]; proj.look_at[k] = look_at[k]; proj.up[k] = up[k]; }
+        proj.angle_deg = proj_angle;
+        proj.extent = proj_extent;
+        auto [image, stat] = !projection.empty() ? renderer.render_projection(bounces, spp, scene, proj, aa)
+                             : adaptive ? renderer.render_adaptive(bounces, spp_min, spp, tolerance, scene, camera,
                                                                  pixel_counts, adaptive_step, device_plan)
                              : progressive ? renderer.render_progressive(bounces, spp, scene, camera, counts, step)
                                            : renderer.render(bounces, spp, scene, camera);     // main.rs:64

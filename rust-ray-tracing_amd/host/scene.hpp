@@ -578,6 +578,57 @@ struct GpuRenderer : Renderer {
         return (flags & RT_FLAG_F32) ? pick_t<float>(pixels, scene, camera) : pick_t<double>(pixels, scene, camera);
     }
 
+    // A camera model the reference lacks (rt_camera_rays: orthographic, panorama, fisheye), path-traced with
+    // rt_render_rays_async: grid x grid rays per pixel on the host, uploaded once, sample s of a pixel starting as
+    // its ray s % grid^2.  One launch on a context of its own; RT_FLAG_F32 and RT_FLAG_ROOT2 are passed on.
+    template <typename T>
+    std::pair<RgbImage, RenderStat> render_projection_t(size_t max_bounces, size_t spp, const Scene& scene,
+                                                        const rt_projection& proj, uint32_t grid) {
+        const auto t0 = std::chrono::steady_clock::now();
+        FlatScene flat = scene.flatten();
+        rt_scene rs = flat.view();
+        RgbImage img{proj.image_width, proj.image_height, {}};
+        const size_t npx = (size_t)img.width * img.height, nrays = npx * grid * grid;
+        img.data.resize(npx * 3);
+        auto chk = [](int rc, const char* what) {
+            if (rc != RT_OK) throw Panic(std::string(what) + ": " + rt_last_error());
+        };
+        std::vector<T> org(3 * nrays), dir(3 * nrays);
+        const uint32_t rflags = flags & (RT_FLAG_F32 | RT_FLAG_ROOT2);
+        chk(rt_camera_rays(&proj, grid, rflags & RT_FLAG_F32, org.data(), dir.data()), "rt_camera_rays");
+        struct Ctx {
+            rt_context* c = nullptr;
+            void* buf[3] = {nullptr, nullptr, nullptr};
+            ~Ctx() {
+                for (void* b : buf) if (b) rt_device_free(c, b);
+                if (c) rt_context_destroy(c);
+            }
+        } x;
+        chk(rt_context_create(0, &x.c), "rt_context_create");
+        chk(rt_context_set_scene(x.c, &rs), "rt_context_set_scene");
+        const size_t bytes = 3 * nrays * sizeof(T);
+        chk(rt_device_alloc(x.c, bytes, &x.buf[0]), "rt_device_alloc");
+        chk(rt_device_alloc(x.c, bytes, &x.buf[1]), "rt_device_alloc");
+        chk(rt_device_alloc(x.c, npx * 3, &x.buf[2]), "rt_device_alloc");
+        chk(rt_memcpy_h2d(x.c, x.buf[0], org.data(), bytes), "rt_memcpy_h2d");
+        chk(rt_memcpy_h2d(x.c, x.buf[1], dir.data(), bytes), "rt_memcpy_h2d");
+        chk(rt_render_rays_async(x.c, npx, (uint32_t)spp, grid * grid, x.buf[0], nullptr, x.buf[1], (uint32_t)max_bounces,
+                                 seed, 0u, rflags, x.buf[2], nullptr, nullptr),
+            "rt_render_rays_async");
+        rt_stats st{};
+        const int rc = rt_context_collect(x.c, nullptr, &st);
+        if (rc == RT_ERR_RANGE) throw Panic(std::string("assertion failed: ") + rt_last_error());
+        chk(rc, "rt_context_collect");
+        chk(rt_memcpy_d2h(x.c, img.data.data(), x.buf[2], npx * 3), "rt_memcpy_d2h");
+        RenderStat stat(std::chrono::steady_clock::now() - t0, npx, st);
+        return {std::move(img), stat};
+    }
+    std::pair<RgbImage, RenderStat> render_projection(size_t max_bounces, size_t spp, const Scene& scene,
+                                                      const rt_projection& proj, uint32_t grid) {
+        return (flags & RT_FLAG_F32) ? render_projection_t<float>(max_bounces, spp, scene, proj, grid)
+                                     : render_projection_t<double>(max_bounces, spp, scene, proj, grid);
+    }
+
   private:
     void render_blocks(const rt_scene& rs, const Camera& camera, uint32_t max_bounces, uint32_t spp, RgbImage& img,
                        rt_stats& total, uint32_t B, bool print_blocks) {

@@ -9,6 +9,7 @@ from .scene import Camera, Dielectric, FlatScene, Lambertian, Metal, Scene, Sphe
 from .renderer import GpuRenderer, Guides, ProgressiveSession, RenderStat, Renderer
 from . import scenes
 from . import parallel
+from . import projections
 from . import toml_scene
 from .toml_scene import Panic, load_scene, scene_from_toml
 

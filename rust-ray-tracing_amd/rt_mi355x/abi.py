@@ -55,6 +55,16 @@ class RtTileRange(ctypes.Structure):
     _fields_ = [("row_begin", u32), ("row_step", u32), ("row_count", u32), ("col_begin", u32), ("col_count", u32)]
 
 
+RT_PROJ_ORTHOGRAPHIC = 0
+RT_PROJ_EQUIRECT = 1
+RT_PROJ_FISHEYE = 2
+
+
+class RtProjection(ctypes.Structure):
+    _fields_ = [("model", u32), ("image_width", u32), ("image_height", u32), ("center", f64 * 3), ("look_at", f64 * 3),
+                ("up", f64 * 3), ("angle_deg", f64), ("extent", f64)]
+
+
 class RtStats(ctypes.Structure):
     _fields_ = [
         ("seconds", f64),
@@ -96,6 +106,11 @@ def RT_KERNEL_QUERY(kernel_id):
     return (kernel_id >> 12) & 1
 
 
+def RT_KERNEL_RAYS(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_RAYS: the caller-ray kernel ran (rt_render_rays_async)."""
+    return (kernel_id >> 13) & 1
+
+
 RT_QUERY_MISS = -1      # include/rt_mi355x.h: rt_query_hits_async's index of a ray that hits nothing
 RT_QUERY_INVALID = -2   # ... and of a ray outside the precondition (not traced)
 
@@ -107,7 +122,8 @@ def kernel_info(kernel_id):
     return {"T": "double" if kernel_id & 1 else "float", "W": (kernel_id >> 1) & 7, "root2": bool((kernel_id >> 4) & 1),
             "mode": (kernel_id >> 5) & 3, "camq": bool((kernel_id >> 7) & 1), "mega": bool((kernel_id >> 8) & 1),
             "split": bool(RT_KERNEL_SPLIT(kernel_id)), "items": bool(RT_KERNEL_ITEMS(kernel_id)),
-            "guides": bool(RT_KERNEL_GUIDES(kernel_id)), "query": bool(RT_KERNEL_QUERY(kernel_id))}
+            "guides": bool(RT_KERNEL_GUIDES(kernel_id)), "query": bool(RT_KERNEL_QUERY(kernel_id)),
+            "rays": bool(RT_KERNEL_RAYS(kernel_id))}
 
 
 def kernel_name(kernel_id):
@@ -116,6 +132,8 @@ def kernel_name(kernel_id):
     if k is None:
         return None
     b = lambda v: "true" if v else "false"
+    if k["rays"]:   # trace_paths_rays<T,W,ROOT2,MEGA> (rays_validate<T> runs ahead of it)
+        return f"trace_paths_rays<{k['T']},{k['W']},{b(k['root2'])},{b(k['mega'])}>"
     if k["query"]:   # query_rays<T,ROOT2,SHARED,MEGA> (SHARED in the CAMQ bit)
         return f"query_rays<{k['T']},{b(k['root2'])},{b(k['camq'])},{b(k['mega'])}>"
     if k["guides"]:   # guide_pixels<T,CAMQ,MEGA>
@@ -155,14 +173,14 @@ EXPORTED = [
     "rt_progressive_bytes", "rt_progressive_begin", "rt_progressive_extend_async", "rt_progressive_end",
     "rt_progressive_extend_map_async", "rt_progressive_snapshot_map_async", "rt_progressive_counts",
     "rt_progressive_error_async", "rt_progressive_map_plan", "rt_progressive_refine", "rt_progressive_refine_items",
-    "rt_render_guides_async", "rt_query_hits_async", "rt_memcpy_h2d",
+    "rt_render_guides_async", "rt_query_hits_async", "rt_memcpy_h2d", "rt_render_rays_async", "rt_camera_rays",
 ]
 
 _lib = None
 
 # The sources the Makefile hashes into rt_version() ("src=<hash>"), in its order (SRC, then HDR).
 KERNEL_SOURCES = ["rt_kernel.hip", "rt_experiments.hpp", "rt_formats.hpp", "rt_common.hpp", "rt_sweep.hpp",
-                  "rt_camera.hpp", "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp",
+                  "rt_camera.hpp", "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_rays.hpp", "rt_projection.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp",
                   "rt_progressive_plan.hpp", "rt_host.hpp", "rt_launch.hpp", "rt_session.hpp", "rt_guides.hpp", "rt_query.hpp"]
 SOURCE_FILES = [os.path.join(PKG_DIR, "csrc", f) for f in KERNEL_SOURCES] + \
                [os.path.join(os.path.dirname(PKG_DIR), "include", "rt_mi355x.h")]
@@ -218,6 +236,8 @@ def load_library(path=None):
     lib.rt_render_split_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp, u32]
     lib.rt_render_guides_async.argtypes = [vp, P(RtCamera), u32, u64, u32, P(RtTileRange), vp, vp, vp, vp, vp]
     lib.rt_query_hits_async.argtypes = [vp, u64, vp, P(f64), vp, u32, vp, vp, vp, vp, vp, vp]
+    lib.rt_render_rays_async.argtypes = [vp, u64, u32, u32, vp, P(f64), vp, u32, u64, u32, u32, vp, vp, vp]
+    lib.rt_camera_rays.argtypes = [P(RtProjection), u32, u32, vp, vp]
     lib.rt_split_plan.argtypes = [u64, u32, u32, P(u32), P(u64)]
     lib.rt_progressive_bytes.argtypes = [u64, u32, u32, u32, P(u64)]
     lib.rt_progressive_begin.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), u64]

@@ -198,6 +198,80 @@ def check_query_into(flags, device, origins, directions, outputs):
     return n, d_org, origin, d_dir, ptrs
 
 
+def _rays_flags(flags):
+    if flags & ~(abi.RT_FLAG_F32 | abi.RT_FLAG_ROOT2):
+        raise ValueError("caller rays are rendered on the live path: mode 'vectorized2' only (root2 is allowed)")
+    return _query_dtype(flags)
+
+
+def _rays_counts(spp, n, R, pixel_base):
+    if isinstance(spp, bool) or not isinstance(spp, (int, np.integer)) or not 1 <= spp <= 1 << 20:
+        raise ValueError(f"spp must be an integer in 1..2^20, not {spp!r}")
+    if not 1 <= R <= spp:
+        raise ValueError(f"rays per pixel must be within 1..spp: directions has {R} rays per pixel, spp is {spp}")
+    if n > 0x7FFFFFFF:
+        raise ValueError("more than 0x7FFFFFFF pixels in one call")
+    if isinstance(pixel_base, bool) or not isinstance(pixel_base, (int, np.integer)) or pixel_base < 0 \
+            or pixel_base + n > 1 << 32:
+        raise ValueError(f"pixel_base must be an integer with pixel_base + n <= 2^32, not {pixel_base!r}")
+
+
+def check_render_rays(flags, spp, origins, directions, pixel_base=0):
+    """GpuRenderer.render_rays' arguments checked before any GPU call.  directions: (n, R, 3) or (n, 3) (R = 1);
+    origins: the same shape, or (3,) for one shared origin.  Returns (origins, directions (n, R, 3), shared), the arrays
+    contiguous in the renderer's precision, a shared origin kept in float64."""
+    dtype = _rays_flags(flags)
+    d = np.asarray(directions)
+    o = np.asarray(origins)
+    for what, a in (("directions", d), ("origins", o)):
+        if a.dtype.kind not in "fiu":
+            raise ValueError(f"{what} must be numbers, not dtype {a.dtype}")
+    if d.ndim not in (2, 3) or d.shape[-1] != 3:
+        raise ValueError(f"directions must have shape (n, R, 3) or (n, 3), not {d.shape}")
+    shared = o.shape == (3,)
+    if not shared and o.shape != d.shape:
+        raise ValueError(f"origins must have shape (3,) (one shared origin) or {d.shape} like directions, not {o.shape}")
+    d = d.reshape(d.shape[0], 1, 3) if d.ndim == 2 else d
+    _rays_counts(spp, d.shape[0], d.shape[1], pixel_base)
+    o = np.ascontiguousarray(o, dtype=np.float64) if shared else np.ascontiguousarray(o, dtype=dtype).reshape(d.shape)
+    return o, np.ascontiguousarray(d, dtype=dtype), shared
+
+
+def check_render_rays_into(flags, device, spp, origins, directions, rgb, linear, pixel_base=0):
+    """GpuRenderer.render_rays_into's arguments checked before any GPU call.  Returns (n, R, d_origins | None,
+    origin | None, d_directions, d_rgb | None, d_linear | None)."""
+    dtype = _rays_flags(flags)
+    cai = getattr(directions, "__cuda_array_interface__", None)
+    if not isinstance(cai, dict):
+        raise TypeError(f"directions must expose __cuda_array_interface__ (a device array), not {type(directions).__name__}")
+    shape = tuple(cai["shape"])
+    if len(shape) not in (2, 3) or shape[-1] != 3:
+        raise ValueError(f"directions must have shape (n, R, 3) or (n, 3), not {shape}")
+    n, R = shape[0], (shape[1] if len(shape) == 3 else 1)
+    _rays_counts(spp, n, R, pixel_base)
+    d_dir = _device_array(directions, "directions", dtype, shape, device)
+    d_org, origin = None, None
+    if hasattr(origins, "__cuda_array_interface__"):
+        d_org = _device_array(origins, "origins", dtype, shape, device)
+    else:
+        origin = np.asarray(origins)
+        if origin.shape != (3,) or origin.dtype.kind not in "fiu":
+            raise ValueError("origins must be a device array shaped like directions or one shared origin of 3 host numbers")
+        origin = np.ascontiguousarray(origin, dtype=np.float64)
+    ptrs = []
+    for name, obj, dt in (("rgb", rgb, np.uint8), ("linear", linear, np.float64)):
+        if obj is None:
+            ptrs.append(None)
+            continue
+        cw = getattr(obj, "__cuda_array_interface__", None)
+        if isinstance(cw, dict) and cw["data"][1]:
+            raise ValueError(f"{name} is read-only")
+        ptrs.append(_device_array(obj, name, dt, (n, 3), device))
+    if ptrs[0] is None and ptrs[1] is None:
+        raise ValueError("no output given (rgb or linear)")
+    return n, R, d_org, origin, d_dir, ptrs[0], ptrs[1]
+
+
 def check_adaptive(spp_min, spp_max, tolerance, plan="host"):
     """GpuRenderer.adaptive's arguments checked before any GPU call: 1 <= spp_min <= spp_max, a tolerance that is
     a number (not NaN), a plan that is "host" or "device".  Returns (spp_min, spp_max, tolerance) as
@@ -619,6 +693,72 @@ class GpuRenderer(Renderer):
         op = origin.ctypes.data_as(ctypes.POINTER(abi.f64)) if origin is not None else None
         abi.check(self.lib, self.lib.rt_query_hits_async(self.ctx, n, d_org, op, d_dir, flags,
                                                          *[ptrs.get(name) for name in QUERY_NAMES], stream))
+        return n
+
+    def render_rays(self, max_bounces, spp, origins, directions, scene, seed=None, pixel_base=0, root2=False,
+                    want_linear=False):
+        """rt_render_rays_async with numpy arrays: full paths for caller-supplied primary rays (include/rt_mi355x.h
+        has the definition; rt_mi355x.projections makes the rays of an orthographic, panorama or fisheye camera).
+        directions: (n, R, 3), or (n, 3) for one ray per pixel, not normalised; sample s of pixel p starts as ray
+        s % R of that pixel.  origins: the same shape, or (3,) for one shared origin.  seed: the RNG key (None: the
+        renderer's); pixel_base: the RNG's pixel of pixel 0 (shards of one frame pass their first pixel).  A pixel
+        with an invalid ray (non-finite, or |d|^2 outside [1e-6, 1e6]) comes back black, its linear value NaN.
+        Returns (rgb [n, 3] u8, linear [n, 3] f64 | None, RtStats, rc)."""
+        flags = self._query_flags(root2)
+        o, d, shared = check_render_rays(flags, spp, origins, directions, pixel_base)   # before any GPU call
+        n, R = d.shape[0], d.shape[1]
+        flat = scene.flatten() if hasattr(scene, "flatten") else scene
+        lib = self.lib
+        if self._scene_flat is not flat:
+            self.set_scene(flat)
+        rgb = np.empty((n, 3), dtype=np.uint8)
+        lin = np.empty((n, 3), dtype=np.float64) if want_linear else None
+        if n == 0:
+            return rgb, lin, abi.RtStats(), abi.RT_OK
+        d_dir, d_org, d_rgb, d_lin = (ctypes.c_void_p() for _ in range(4))
+        try:
+            abi.check(lib, lib.rt_device_alloc(self.ctx, d.nbytes, ctypes.byref(d_dir)))
+            abi.check(lib, lib.rt_memcpy_h2d(self.ctx, d_dir, d.ctypes.data, d.nbytes))
+            if not shared:
+                abi.check(lib, lib.rt_device_alloc(self.ctx, o.nbytes, ctypes.byref(d_org)))
+                abi.check(lib, lib.rt_memcpy_h2d(self.ctx, d_org, o.ctypes.data, o.nbytes))
+            abi.check(lib, lib.rt_device_alloc(self.ctx, n * 3, ctypes.byref(d_rgb)))
+            if want_linear:
+                abi.check(lib, lib.rt_device_alloc(self.ctx, n * 3 * 8, ctypes.byref(d_lin)))
+            origin = o.ctypes.data_as(ctypes.POINTER(abi.f64)) if shared else None
+            abi.check(lib, lib.rt_render_rays_async(self.ctx, n, spp, R, None if shared else d_org, origin, d_dir,
+                                                    max_bounces, self.seed if seed is None else seed, pixel_base, flags,
+                                                    d_rgb, d_lin if want_linear else None, None))
+            st = abi.RtStats()
+            rc = abi.check(lib, lib.rt_context_collect(self.ctx, None, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
+            abi.check(lib, lib.rt_memcpy_d2h(self.ctx, rgb.ctypes.data, d_rgb, n * 3))
+            if want_linear:
+                abi.check(lib, lib.rt_memcpy_d2h(self.ctx, lin.ctypes.data, d_lin, n * 3 * 8))
+        finally:
+            for p in (d_dir, d_org, d_rgb, d_lin):
+                if p:
+                    lib.rt_device_free(self.ctx, p)
+        return rgb, lin, st, rc
+
+    def render_rays_into(self, max_bounces, spp, origins, directions, *, rgb=None, linear=None, seed=None, pixel_base=0,
+                         root2=False, stream=None):
+        """rt_render_rays_async on device arrays in place, without a copy: directions (n, R, 3) or (n, 3) and the
+        outputs given (rgb (n, 3) uint8, linear (n, 3) float64) are objects exposing __cuda_array_interface__ (torch
+        ROCm tensors do), C-contiguous, on the renderer's device, the rays in the renderer's precision.  origins: such
+        an array shaped like directions, or 3 host numbers for one shared origin.  The scene is the one last set
+        (set_scene).  stream: an integer stream handle (None: the null stream); the call is asynchronous on it, and
+        collect-time errors (RT_ERR_RANGE) are the caller's to collect.  Returns the number of pixels."""
+        flags = self._query_flags(root2)
+        n, R, d_org, origin, d_dir, d_rgb, d_lin = check_render_rays_into(
+            flags, self.device, spp, origins, directions, rgb, linear, pixel_base)
+        if stream is not None and (isinstance(stream, bool) or not isinstance(stream, int)):
+            raise TypeError(f"stream must be an integer stream handle or None, not {stream!r}")
+        if self._scene_flat is None:
+            raise RuntimeError("render_rays_into needs a scene: call set_scene first")
+        op = origin.ctypes.data_as(ctypes.POINTER(abi.f64)) if origin is not None else None
+        abi.check(self.lib, self.lib.rt_render_rays_async(self.ctx, n, spp, R, d_org, op, d_dir, max_bounces,
+                                                          self.seed if seed is None else seed, pixel_base, flags,
+                                                          d_rgb, d_lin, stream))
         return n
 
     def begin_progressive(self, max_bounces, spp_capacity, scene, camera, tile_range=None, max_bytes=0):
