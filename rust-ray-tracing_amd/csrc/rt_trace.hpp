@@ -8,11 +8,20 @@
 
 namespace rt {
 
-// Wave-uniform issue state, parked in LDS between refills for the same reason.
-// need: slots opened since their pixel's camera candidate list was last built (camera batches)
-struct IssueState { uint32_t busy, cur, cur_next, cur_pix, cur_row, cur_col, drained, qhead, qcount, blk_next, blk_end, need; };
+// Wave-uniform issue state, parked in LDS between refills for the same reason.  Every word is read into an SGPR
+// through a VALU instruction and written back through another, so the words are few and a call touches only the
+// ones it needs: a batch served whole from the open item (issue()'s fast path) reads the first five, in two LDS
+// reads, and writes cur_next alone.
+//   flags: the small fields, kIS*: busy (slots with samples in flight), need (slots opened since their pixel's
+//          camera candidate list was last built), nolist (slots whose pixel has no list, pixel_list's 0xFFFF: its
+//          batches run camera_sweep), cur (the slot being issued), drained (no item left to claim)
+//   q:     the camera queue, head | count << 16 (both <= kQCap)
+struct alignas(16) IssueState { uint32_t cur_next, cur_pix, cur_row, cur_col, flags, q, blk_next, blk_end; };
 // ... of the sample-parallel kernels (SPLIT): cur_end, the end of the item being issued (the others stop at spp)
-struct IssueStateS { uint32_t busy, cur, cur_next, cur_pix, cur_row, cur_col, drained, qhead, qcount, blk_next, blk_end, need, cur_end; };
+struct alignas(16) IssueStateS { uint32_t cur_next, cur_pix, cur_row, cur_col, flags, q, blk_next, blk_end, cur_end; };
+constexpr uint32_t kISBusy = 0, kISNeed = 8, kISNoList = 16, kISCur = 24;   // bit offsets in flags: 8, 8, 8 and 3 bits
+constexpr uint32_t kISDrained = 1u << 27;
+static_assert(kSlots <= 8u, "a slot mask is 8 bits of IssueState::flags, a slot index 3");
 
 // Work items (pixels) are claimed in blocks.  One global counter counts blocks, and block j's items
 // are a fixed function of j (guided_block): sizes G, G/2, ..., 2 while more than G T, ..., 2T items

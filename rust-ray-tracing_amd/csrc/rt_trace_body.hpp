@@ -52,7 +52,7 @@
     if constexpr (SPLIT) {
         if (lane == 0) s_is[wave] = IssueStateS{};   // cur_next == cur_end: no item open
     } else {
-        if (lane == 0) s_is[wave] = IssueState{0u, 0u, cold_args<T>()->spp, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (lane == 0) s_is[wave] = IssueState{cold_args<T>()->spp, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     }
     // The workgroup's first block is block blockIdx.x, taken without an atomic (the counter's claims
     // start at gridDim.x): the launch's opening burst of one global atomic per workgroup is gone.
@@ -120,25 +120,37 @@
     // Camera batches on the live path: pixels whose camera candidate list is empty finish at claim time
     // (not SPLIT: its kernels never reduce a pixel; such a pixel is traced, its samples write e = 0)
     constexpr bool kDirectSky = CAMQ && MODE == kModeV2 && !SPLIT;
+    // i_mask: the slots the samples were taken from (wave-uniform).
     auto issue = [&](unsigned long long want, uint32_t& i_sid, uint32_t& i_slot, uint32_t& i_pix,
-                     uint32_t& i_row, uint32_t& i_col) -> bool {
+                     uint32_t& i_row, uint32_t& i_col, uint32_t& i_mask) -> bool {
+        i_mask = 0u;
+        if (want == 0ull) return false;   // nothing asked: the state stays as it is
         const uint32_t spp = cold_args<T>()->spp;
-        bool got = false;
-        uint32_t busy = __builtin_amdgcn_readfirstlane(s_is[wave].busy);
-        uint32_t cur = __builtin_amdgcn_readfirstlane(s_is[wave].cur);
         uint32_t cur_next = __builtin_amdgcn_readfirstlane(s_is[wave].cur_next);
+        uint32_t cur_end = spp;   // the open item's last sample + 1
+        if constexpr (SPLIT) cur_end = __builtin_amdgcn_readfirstlane(s_is[wave].cur_end);
+        uint32_t flags = __builtin_amdgcn_readfirstlane(s_is[wave].flags);
         uint32_t cur_pix = __builtin_amdgcn_readfirstlane(s_is[wave].cur_pix);
         uint32_t cur_row = __builtin_amdgcn_readfirstlane(s_is[wave].cur_row);
         uint32_t cur_col = __builtin_amdgcn_readfirstlane(s_is[wave].cur_col);
-        bool drained = __builtin_amdgcn_readfirstlane(s_is[wave].drained) != 0u;
+        uint32_t cur = (flags >> kISCur) & 7u;
+        // The common call: the open item holds every sample asked for (at 512 spp, seven of a pixel's eight
+        // batches).  Only cur_next changes.  A drained wave has no open item (cur_next == cur_end).
+        const uint32_t nwant = (uint32_t)__popcll(want);
+        if (cur_end - cur_next >= nwant) {
+            const bool isw = (want >> lane) & 1ull;
+            if (isw) { i_sid = cur_next + lanes_below(want); i_slot = cur; i_pix = cur_pix; i_row = cur_row; i_col = cur_col; }
+            if (lane == 0) s_is[wave].cur_next = cur_next + nwant;
+            i_mask = 1u << cur;
+            return isw;
+        }
+        // The flags stay packed, one SGPR, across the pixel's cone walk and finish_sky_direct below.
+        bool got = false;
         uint32_t blk_next = __builtin_amdgcn_readfirstlane(s_is[wave].blk_next);
         uint32_t blk_end = __builtin_amdgcn_readfirstlane(s_is[wave].blk_end);
-        uint32_t opened = 0, listed = 0;
-        uint32_t cur_end = spp;   // the open item's last sample + 1
-        if constexpr (SPLIT) cur_end = __builtin_amdgcn_readfirstlane(s_is[wave].cur_end);
-        while (want != 0ull && !drained) {
+        while (want != 0ull && (flags & kISDrained) == 0u) {
             if (cur_next == cur_end) {
-                const uint32_t avail = ~busy & ((1u << kSlots) - 1u);
+                const uint32_t avail = ~(flags >> kISBusy) & ((1u << kSlots) - 1u);
                 if (avail == 0u) break;   // every slot waits for straggler rays
                 const auto& q = *cold_args<T>();
                 uint32_t item = blk_next;
@@ -172,12 +184,13 @@
                         }
                     }
                     it = __builtin_amdgcn_readfirstlane(it);
-                    if (it == 0xFFFFFFFFu) { drained = true; break; }
+                    if (it == 0xFFFFFFFFu) { flags |= kISDrained; break; }
                     item = it;
                     blk_next = __builtin_amdgcn_readfirstlane(nb);
                     blk_end = __builtin_amdgcn_readfirstlane(ne);
                 }
                 const uint32_t s = __builtin_ctz(avail);
+                uint32_t sbits = (1u << (kISBusy + s)) | (CAMQ ? 1u << (kISNeed + s) : 0u);   // the slot's flags once open
                 uint32_t first = 0;
                 if constexpr (ITEMS) {   // item -> its 16-byte record {pixel, first, end}: wave-uniform scalar loads
                     const cptr<MapItem> tab = (cptr<MapItem>)__builtin_assume_aligned(cold_items_args<T>()->items, 16);
@@ -218,7 +231,7 @@
                         // one means no primary ray of the pixel can hit a sphere, so every sample escapes
                         // at bounce 0 and the pixel is finished here without tracing (finish_sky_direct);
                         // its slot stays free
-                        const uint32_t nl = pixel_list<T, MEGA>(cur_col, cur_row, s_clist[wave][s]);
+                        const uint32_t nl = __builtin_amdgcn_readfirstlane(pixel_list<T, MEGA>(cur_col, cur_row, s_clist[wave][s]));
                         if (nl == 0u) {
                             const uint32_t ss_keep = kParkSS ? *ssp : 0u;   // the stage is overwritten
                             finish_sky_direct<T>(item, cur_col, cur_row, cur_pix, s_hist[wave], s_stage[wave]);
@@ -230,13 +243,12 @@
                             if (lane == 0) { wcount[wave][0] += spp; wcount[wave][3] += spp; wcount[wave][2] += 1u; }
                             continue;
                         }
-                        listed |= 1u << s;
+                        sbits = (1u << (kISBusy + s)) | ((nl == 0xFFFFu ? 1u : 0u) << (kISNoList + s));   // listed: no need
                     }
                 }
                 if (lane == 0) { s_slotpix[wave][s] = cur_pix; s_item[wave][s] = item; }
                 if (lane == s) slot_left = cur_end - first;
-                busy |= 1u << s;
-                opened |= 1u << s;
+                flags = (flags & ~((1u << (kISNeed + s)) | (1u << (kISNoList + s)) | (7u << kISCur))) | sbits | (s << kISCur);
                 cur = s;
                 cur_next = first;
             }
@@ -247,12 +259,12 @@
             if (mine) { got = true; i_sid = cur_next + r; i_slot = cur; i_pix = cur_pix; i_row = cur_row; i_col = cur_col; }
             want &= ~__ballot(mine);
             cur_next += take;
+            i_mask |= (take != 0u ? 1u : 0u) << cur;
         }
         if (lane == 0) {
-            s_is[wave].busy = busy; s_is[wave].cur = cur; s_is[wave].cur_next = cur_next; s_is[wave].cur_pix = cur_pix;
-            s_is[wave].cur_row = cur_row; s_is[wave].cur_col = cur_col; s_is[wave].drained = drained ? 1u : 0u;
-            s_is[wave].blk_next = blk_next; s_is[wave].blk_end = blk_end;
-            if (CAMQ) s_is[wave].need |= opened & ~listed;
+            s_is[wave].cur_next = cur_next; s_is[wave].cur_pix = cur_pix; s_is[wave].cur_row = cur_row;
+            s_is[wave].cur_col = cur_col; s_is[wave].flags = flags; s_is[wave].blk_next = blk_next;
+            s_is[wave].blk_end = blk_end;
             if constexpr (SPLIT) s_is[wave].cur_end = cur_end;
         }
         return got;
@@ -296,8 +308,8 @@
             // places any spill code here rather than in the sphere sweeps
             if constexpr (SPLIT) {
                 if (left == 0u) {   // item complete: free the slot (finish_records reduces the pixel)
-                    const uint32_t b = __builtin_amdgcn_readfirstlane(s_is[wave].busy);
-                    if (lane == 0) s_is[wave].busy = b & ~(1u << s);
+                    const uint32_t b = __builtin_amdgcn_readfirstlane(s_is[wave].flags);
+                    if (lane == 0) s_is[wave].flags = b & ~(1u << (kISBusy + s));
                 }
             } else if (__builtin_expect((left & ~kSlotNZ) == 0u, 0)) {
                 const uint32_t ss_keep = kParkSS ? *ssp : 0u;   // finish_pixel overwrites the stage
@@ -311,8 +323,8 @@
                     *ssp = ss_keep;
                 }
                 if (lane == 0) wcount[wave][2] += K;
-                const uint32_t b = __builtin_amdgcn_readfirstlane(s_is[wave].busy);
-                if (lane == 0) s_is[wave].busy = b & ~(1u << s);
+                const uint32_t b = __builtin_amdgcn_readfirstlane(s_is[wave].flags);
+                if (lane == 0) s_is[wave].flags = b & ~(1u << (kISBusy + s));
             }
         }
     };
@@ -320,7 +332,9 @@
     // CAMQ: one full-wave batch of primary rays.  Returns false when no sample could be issued.
     auto camera_batch = [&]() -> bool {
         uint32_t bsid = 0, bslot = 0, bpix = 0, brow = 0, bcol = 0;
-        const bool v = issue(~0ull, bsid, bslot, bpix, brow, bcol);
+        // smask: the batch's pixel slots (one, or two where a pixel's samples end inside the batch)
+        uint32_t smask = 0;
+        const bool v = issue(~0ull, bsid, bslot, bpix, brow, bcol, smask);
         const unsigned long long vm = __ballot(v);
         if (vm == 0ull) return false;
         V3<T> bd = mk(T(0), T(0), T(0));
@@ -342,29 +356,24 @@
         T bt = T(0);
         int bi = -1;
         {
-            // the batch's pixel slots (one, or two where a pixel's samples end inside the batch)
-            uint32_t smask = 0;
-            for (unsigned long long m = vm; m != 0ull;) {
-                const uint32_t sl = __builtin_amdgcn_readlane(bslot, (int)__builtin_ctzll(m));
-                smask |= 1u << sl;
-                m &= ~__ballot(v && bslot == sl);
-            }
-            // each newly opened pixel's candidate list (one cone walk per pixel, not per batch)
-            uint32_t need = __builtin_amdgcn_readfirstlane(s_is[wave].need) & smask;
+            // each newly opened pixel's candidate list (one cone walk per pixel, not per batch).  The flags are read
+            // again here, not handed over by issue(): an SGPR held across the camera ray's arithmetic is spilled.
+            uint32_t fl = __builtin_amdgcn_readfirstlane(s_is[wave].flags);
+            uint32_t need = (fl >> kISNeed) & smask;
             if (need != 0u) {
-                if (lane == 0) s_is[wave].need = s_is[wave].need & ~need;
+                fl &= ~(need << kISNeed);
                 const uint32_t iw = cold_args<T>()->W;
                 while (need != 0u) {
                     const uint32_t sl = (uint32_t)__builtin_ctz(need);
                     need &= need - 1u;
                     const uint32_t pxi = __builtin_amdgcn_readfirstlane(s_slotpix[wave][sl]);
                     const uint32_t row = pxi / iw;
-                    (void)pixel_list<T, MEGA>(pxi - row * iw, row, s_clist[wave][sl]);
+                    const uint32_t nl = __builtin_amdgcn_readfirstlane(pixel_list<T, MEGA>(pxi - row * iw, row, s_clist[wave][sl]));
+                    if (nl == 0xFFFFu) fl |= 1u << (kISNoList + sl);   // (issue() cleared the bit when it opened the slot)
                 }
+                if (lane == 0) s_is[wave].flags = fl;
             }
-            bool listed = true;
-            for (uint32_t m = smask; m != 0u; m &= m - 1u)
-                if (__builtin_amdgcn_readfirstlane(s_clist[wave][__builtin_ctz(m)][0]) == 0xFFFFu) listed = false;
+            const bool listed = ((fl >> kISNoList) & smask) == 0u;
             if (listed) bi = camera_listed<T, ROOT2, SC>(v, bd, bt, s_clist[wave], smask);
             else bi = camera_sweep<T, ROOT2, SC, MEGA>(v, bd, bt);   // whole wave: lanes are spheres in the cull
         }
@@ -374,8 +383,8 @@
         const bool term = v && (skyhit || depth == 1u);
         const bool push = v && !term;
         const unsigned long long pm = __ballot(push);
-        const uint32_t qhead = __builtin_amdgcn_readfirstlane(s_is[wave].qhead);
-        const uint32_t qcount = __builtin_amdgcn_readfirstlane(s_is[wave].qcount);
+        const uint32_t q = __builtin_amdgcn_readfirstlane(s_is[wave].q);
+        const uint32_t qhead = q & 0xFFFFu, qcount = q >> 16;
         if (push) {
             const uint32_t e = (qhead + qcount + lanes_below(pm)) % QN;
             q_sid[wave][e] = bsid | (bslot << 29);
@@ -383,7 +392,7 @@
             q_t[wave][e] = bt;
             q_d[wave][0][e] = bd.x; q_d[wave][1][e] = bd.y; q_d[wave][2][e] = bd.z;
         }
-        if (lane == 0) s_is[wave].qcount = qcount + (uint32_t)__popcll(pm);
+        if (lane == 0) s_is[wave].q = q + ((uint32_t)__popcll(pm) << 16);
         terminate(term, skyhit, skyhit ? 0u : depth, bslot, bsid, mk(T(1.0), T(1.0), T(1.0)), bd);
         return true;
     };
@@ -395,13 +404,16 @@
             // ---- top up the queue with camera batches, then free lanes pop primary-ray hits ----
             const unsigned long long freem = __ballot(!live);
             const uint32_t nfree = (uint32_t)__popcll(freem);
+            uint32_t q = 0;
             for (;;) {
-                const uint32_t qcount = __builtin_amdgcn_readfirstlane(s_is[wave].qcount);
-                if (qcount >= nfree || qcount + 64u > QN) break;
-                if (!camera_batch()) break;
+                q = __builtin_amdgcn_readfirstlane(s_is[wave].q);
+                if ((q >> 16) >= nfree || (q >> 16) + 64u > QN) break;
+                if (!camera_batch()) {   // nothing issued.  Read again: q held across the call would be one more SGPR to spill
+                    q = __builtin_amdgcn_readfirstlane(s_is[wave].q);
+                    break;
+                }
             }
-            const uint32_t qhead = __builtin_amdgcn_readfirstlane(s_is[wave].qhead);
-            const uint32_t qcount = __builtin_amdgcn_readfirstlane(s_is[wave].qcount);
+            const uint32_t qhead = q & 0xFFFFu, qcount = q >> 16;
             const uint32_t take = min(nfree, qcount);
             const uint32_t r = lanes_below(freem);
             if (!live && r < take) {
@@ -420,11 +432,11 @@
                 live = true;
                 scat = true;
             }
-            if (lane == 0) { s_is[wave].qhead = (qhead + take) % QN; s_is[wave].qcount = qcount - take; }
+            if (lane == 0) s_is[wave].q = ((qhead + take) % QN) | ((qcount - take) << 16);
         } else {
             // ---- hand free lanes the next samples (opening new pixel slots as needed) ----
-            uint32_t nsid = 0, nslot = 0;
-            fresh = issue(__ballot(!live), nsid, nslot, npix, frow, fcol);
+            uint32_t nsid = 0, nslot = 0, nmask = 0;
+            fresh = issue(__ballot(!live), nsid, nslot, npix, frow, fcol, nmask);
             if (fresh) ss_set(nsid | (nslot << 29));
         }
         // ---- next rays: camera rays for fresh lanes, scattered rays for last iteration's hits ----
