@@ -132,6 +132,20 @@ void oracle_to_u8(const double rgb[3], uint8_t out[3], int* panics) {
             for (int w = 0; w < 4; ++w) r[(size_t)w * n + i] = b[w];                                              \
             ua[i] = u01_##sfx(b); ub[i] = u01b_##sfx(b);                                                          \
         }                                                                                                         \
+    }                                                                                                             \
+    /* the next-ray stage on its own (oracle_impl.h next_ray_n, get_ray_n; tests/test_gpu_scatter.py) */          \
+    int oracle_next_ray_##sfx##_n(const or_scene* sc, uint64_t seed, uint32_t mode, size_t n, const REAL* o,      \
+                                  const REAL* d, const int32_t* hit_i, const REAL* hit_t, const uint32_t* sid,    \
+                                  const uint32_t* pix, const uint32_t* k, const REAL* colour_in, REAL* o_out,     \
+                                  REAL* d_out, REAL* colour_out, REAL* nrm_out, uint8_t* front_out,               \
+                                  uint8_t* code_out) {                                                            \
+        return next_ray_n_##sfx(sc, seed, mode, n, o, d, hit_i, hit_t, sid, pix, k, colour_in, o_out, d_out,      \
+                                colour_out, nrm_out, front_out, code_out);                                        \
+    }                                                                                                             \
+    int oracle_get_ray_##sfx##_n(const or_camera* cam, uint64_t seed, size_t n, const uint32_t* col,              \
+                                 const uint32_t* row, const uint32_t* pix, const uint32_t* sid, REAL* o_out,      \
+                                 REAL* d_out) {                                                                   \
+        return get_ray_n_##sfx(cam, seed, n, col, row, pix, sid, o_out, d_out);                                   \
     }
 ORACLE_PROBES(double, f64)
 ORACLE_PROBES(float, f32)

@@ -114,7 +114,29 @@ void oracle_get_ray_f64(const or_camera* cam, uint32_t col, uint32_t row, uint32
     void oracle_refract_##sfx##_n(const REAL* v, const REAL* nn, const REAL* ratio, REAL* out, size_t n);         \
     void oracle_q8_##sfx##_n(const REAL* v, uint8_t* out, size_t n);                                              \
     void oracle_draw_##sfx##_n(const uint32_t* sid, const uint32_t* pix, const uint32_t* k, const uint32_t* stream, \
-                               uint32_t k0, uint32_t k1, uint32_t* r, REAL* ua, REAL* ub, size_t n);
+                               uint32_t k0, uint32_t k1, uint32_t* r, REAL* ua, REAL* ub, size_t n);           \
+    /* The next-ray stage on its own, n lanes: lane j's ray (o, d) has hit sphere hit_i[j] at root hit_t[j] on    \
+     * bounce k[j] of sample sid[j] of pixel pix[j].  mode 0: the packed hit record (PackedHitRecords::finalize:  \
+     * packed length, fused dot) and scatter; 1: the scalar one (normal over the signed radius, plain dot).       \
+     * o_out: the hit point, d_out: the scattered direction, colour_out = colour_in * attenuation.  Diagnostics   \
+     * (may be NULL): nrm_out the normal against the ray, front_out, code_out the OR_BRANCH_* code.  Returns 0,   \
+     * or 1 on bad arguments (a hit index outside the scene among them). */                                       \
+    int oracle_next_ray_##sfx##_n(const or_scene* sc, uint64_t seed, uint32_t mode, size_t n, const REAL* o,      \
+                                  const REAL* d, const int32_t* hit_i, const REAL* hit_t, const uint32_t* sid,    \
+                                  const uint32_t* pix, const uint32_t* k, const REAL* colour_in, REAL* o_out,     \
+                                  REAL* d_out, REAL* colour_out, REAL* nrm_out, uint8_t* front_out,               \
+                                  uint8_t* code_out);                                                             \
+    /* Camera::get_ray for n (col, row, pix, sid). */                                                             \
+    int oracle_get_ray_##sfx##_n(const or_camera* cam, uint64_t seed, size_t n, const uint32_t* col,              \
+                                 const uint32_t* row, const uint32_t* pix, const uint32_t* sid, REAL* o_out,      \
+                                 REAL* d_out);
+/* What scatter did (oracle_next_ray_*_n's code_out). */
+#define OR_BRANCH_LAMBERTIAN 0
+#define OR_BRANCH_NEAR_ZERO 1         /* lambertian, the near_zero fallback to the normal */
+#define OR_BRANCH_METAL 2
+#define OR_BRANCH_CANNOT_REFRACT 3    /* dielectric: ratio * sin > 1 */
+#define OR_BRANCH_SCHLICK_REFLECT 4   /* dielectric: reflectance above the draw */
+#define OR_BRANCH_REFRACT 5
 ORACLE_PROBE_DECLS(double, f64)
 ORACLE_PROBE_DECLS(float, f32)
 

@@ -203,6 +203,18 @@ typedef struct {
     uint32_t mat[4];
 } SFX(phit);
 
+/* What hit_packed records for lane l at `root` of the sphere at (cx, cy, cz): objects.rs:279-280 and update. */
+static inline void SFX(record_root)(const SFX(prays)* R, int l, REAL root, REAL cx, REAL cy, REAL cz, uint32_t mat,
+                                    SFX(phit)* H) {
+    REAL lx = R->ox[l] + R->dx[l] * root;                                              /* at_t, ray.rs:102-104 */
+    REAL ly = R->oy[l] + R->dy[l] * root;
+    REAL lz = R->oz[l] + R->dz[l] * root;
+    H->nx[l] = lx - cx; H->ny[l] = ly - cy; H->nz[l] = lz - cz;                        /* :280 */
+    H->t[l] = root;
+    H->hit[l] = 1;
+    H->mat[l] = mat;
+}
+
 /* Sphere::hit_packed, objects.rs:249-290, folded into PackedHitRecords::update (objects.rs:140-155). */
 static inline void SFX(hit_packed)(const SFX(prays)* R, REAL cx, REAL cy, REAL cz, REAL rad, uint32_t mat,
                                    SFX(phit)* H, uint32_t flags) {
@@ -230,15 +242,7 @@ static inline void SFX(hit_packed)(const SFX(prays)* R, REAL cx, REAL cy, REAL c
         REAL root = r1v ? r1 : r2;                                                     /* :275 */
         int valid = (r1v | r2v) & R->en[l];                                            /* :277 */
         /* update: ties -> later sphere wins (t <= best), objects.rs:141 */
-        if (valid && root <= H->t[l]) {
-            REAL lx = R->ox[l] + R->dx[l] * root;                                      /* at_t, ray.rs:102-104 */
-            REAL ly = R->oy[l] + R->dy[l] * root;
-            REAL lz = R->oz[l] + R->dz[l] * root;
-            H->nx[l] = lx - cx; H->ny[l] = ly - cy; H->nz[l] = lz - cz;                /* :280 */
-            H->t[l] = root;
-            H->hit[l] = 1;
-            H->mat[l] = mat;
-        }
+        if (valid && root <= H->t[l]) SFX(record_root)(R, l, root, cx, cy, cz, mat, H);
     }
 }
 
@@ -260,20 +264,24 @@ static inline void SFX(finalize)(const SFX(prays)* R, SFX(phit)* H) {
 }
 
 /* Material::get_hit_result for one lane: materials.rs:54-63 (lambertian), 92-97 (metal),
- * 128-147 (dielectric).  Writes the scattered ray; returns attenuation. */
-static inline void SFX(scatter)(const SFX(mat_r)* m, V3 d, V3 p, V3 n, int front, uint32_t pix, uint32_t sid,
-                                uint32_t k, uint32_t k0, uint32_t k1, V3* od, REAL att[3]) {
+ * 128-147 (dielectric).  Writes the scattered ray; returns attenuation.  *branch (diagnostics of the next-ray
+ * probe below; may be NULL) receives the OR_BRANCH_* code (oracle.h) of the path taken. */
+static inline void SFX(scatter_dx)(const SFX(mat_r)* m, V3 d, V3 p, V3 n, int front, uint32_t pix, uint32_t sid,
+                                   uint32_t k, uint32_t k0, uint32_t k1, V3* od, REAL att[3], int* branch) {
     uint32_t r[4];
+    int code;
     SFX(draw)(sid, pix, k, 2u, k0, k1, r);
     (void)p;
     if (m->kind == 0u) {
         V3 sd = SFX(add)(SFX(unit_vec)(SFX(u01)(r), SFX(u01b)(r)), n);
-        if (SFX(near_zero)(sd)) sd = n;
+        code = OR_BRANCH_LAMBERTIAN;
+        if (SFX(near_zero)(sd)) { sd = n; code = OR_BRANCH_NEAR_ZERO; }
         *od = sd;
         att[0] = m->ar; att[1] = m->ag; att[2] = m->ab;
     } else if (m->kind == 1u) {
         V3 rv = SFX(add)(SFX(reflect)(d, n), SFX(mul)(SFX(unit_vec)(SFX(u01)(r), SFX(u01b)(r)), m->fuzz));
         *od = rv;
+        code = OR_BRANCH_METAL;
         att[0] = m->ar; att[1] = m->ag; att[2] = m->ab;
     } else {
         REAL ratio = front ? (REAL)1.0 / m->ior : m->ior;
@@ -293,8 +301,14 @@ static inline void SFX(scatter)(const SFX(mat_r)* m, V3 d, V3 p, V3 n, int front
             refl = refl_p > SFX(u01)(r);
         }
         *od = refl ? SFX(reflect)(d, nn) : SFX(refract)(d, nn, ratio);
+        code = cannot ? OR_BRANCH_CANNOT_REFRACT : (refl ? OR_BRANCH_SCHLICK_REFLECT : OR_BRANCH_REFRACT);
         att[0] = (REAL)1.0; att[1] = (REAL)1.0; att[2] = (REAL)1.0;
     }
+    if (branch) *branch = code;
+}
+static inline void SFX(scatter)(const SFX(mat_r)* m, V3 d, V3 p, V3 n, int front, uint32_t pix, uint32_t sid,
+                                uint32_t k, uint32_t k0, uint32_t k1, V3* od, REAL att[3]) {
+    SFX(scatter_dx)(m, d, p, n, front, pix, sid, k, k0, k1, od, att, NULL);
 }
 
 /* sky gradient of trace_vectorized2's final pass, ray_tracing.rs:490-494 */
@@ -611,6 +625,15 @@ static int SFX(scene_hit_scalar)(const SFX(scene_r)* S, V3 o, V3 d, REAL* t_out,
     return found;
 }
 
+/* The scalar path's hit record at root t of sphere i: Ray::at (ray.rs:28-30), the outward normal over the signed
+ * radius (objects.rs:242) and HitRecord::new's front face and flip (objects.rs:69-73). */
+static inline void SFX(hit_record_scalar)(const SFX(scene_r)* S, V3 o, V3 d, REAL t, uint32_t i, V3* p, V3* n, int* front) {
+    *p = SFX(add)(o, SFX(mul)(d, t));
+    V3 outw = SFX(dvs)(SFX(sub)(*p, SFX(mk)(S->cx[i], S->cy[i], S->cz[i])), S->r[i]);
+    *front = SFX(dot)(d, outw) < (REAL)0.0;
+    *n = *front ? outw : SFX(neg)(outw);
+}
+
 static void SFX(trace_ray_scalar)(const SFX(scene_r)* S, V3 o, V3 d, uint32_t depth, uint32_t pix, uint32_t sid,
                                   uint32_t k0, uint32_t k1, REAL out[3], uint64_t* segs) {
     REAL cr = 1, cg = 1, cb = 1;                                                       /* :266-269 */
@@ -620,11 +643,9 @@ static void SFX(trace_ray_scalar)(const SFX(scene_r)* S, V3 o, V3 d, uint32_t de
         REAL t;
         uint32_t i;
         if (SFX(scene_hit_scalar)(S, o, d, &t, &i)) {
-            V3 p = SFX(add)(o, SFX(mul)(d, t));                                        /* Ray::at, ray.rs:28-30 */
-            V3 outw = SFX(dvs)(SFX(sub)(p, SFX(mk)(S->cx[i], S->cy[i], S->cz[i])), S->r[i]);   /* objects.rs:242 */
-            int front = SFX(dot)(d, outw) < (REAL)0.0;                                /* HitRecord::new, objects.rs:69-73 */
-            V3 n = front ? outw : SFX(neg)(outw);
-            V3 nd;
+            V3 p, n, nd;
+            int front;
+            SFX(hit_record_scalar)(S, o, d, t, i, &p, &n, &front);
             REAL att[3];
             SFX(scatter)(&S->mats[S->mat[i]], d, p, n, front, pix, sid, k, k0, k1, &nd, att);
             cr = cr * att[0]; cg = cg * att[1]; cb = cb * att[2];                      /* :280 */
@@ -857,5 +878,120 @@ int SFX(oracle_nearest_hit)(const or_scene* sc, uint32_t mode, size_t n, const R
         }
     }
     free(S.cx);
+    return 0;
+}
+
+/* ---- the next-ray stage on its own (tests/scatter_cases.py, tests/test_gpu_scatter.py) ---- */
+/* The scene and the camera in REAL, converted as oracle_render converts them. */
+static int SFX(scene_from)(const or_scene* sc, SFX(scene_r)* S) {
+    S->n = sc->n_spheres;
+    S->cx = (REAL*)malloc(sizeof(REAL) * (4 * (size_t)S->n + 4));
+    S->mats = (SFX(mat_r)*)malloc(sizeof(SFX(mat_r)) * ((size_t)sc->n_materials + 1));
+    if (!S->cx || !S->mats) { free(S->cx); free(S->mats); return 0; }
+    S->cy = S->cx + S->n + 1; S->cz = S->cy + S->n + 1; S->r = S->cz + S->n + 1;
+    S->mat = sc->material;
+    for (uint32_t i = 0; i < S->n; ++i) {
+        S->cx[i] = (REAL)sc->center[3 * i]; S->cy[i] = (REAL)sc->center[3 * i + 1];
+        S->cz[i] = (REAL)sc->center[3 * i + 2]; S->r[i] = (REAL)sc->radius[i];
+    }
+    for (uint32_t i = 0; i < sc->n_materials; ++i) {
+        const or_material* m = &sc->materials[i];
+        SFX(mat_r)* o = &S->mats[i];
+        o->kind = m->kind; o->hollow = m->hollow;
+        o->ar = (REAL)m->albedo[0]; o->ag = (REAL)m->albedo[1]; o->ab = (REAL)m->albedo[2];
+        o->fuzz = (REAL)m->fuzz; o->ior = (REAL)m->ior;
+    }
+    return 1;
+}
+static SFX(cam_r) SFX(cam_from)(const or_camera* cam) {
+    SFX(cam_r) C;
+    C.W = cam->image_width; C.H = cam->image_height;
+    C.center = SFX(mk)((REAL)cam->center[0], (REAL)cam->center[1], (REAL)cam->center[2]);
+    C.ulc = SFX(mk)((REAL)cam->ulc[0], (REAL)cam->ulc[1], (REAL)cam->ulc[2]);
+    C.vu = SFX(mk)((REAL)cam->vu[0], (REAL)cam->vu[1], (REAL)cam->vu[2]);
+    C.vv = SFX(mk)((REAL)cam->vv[0], (REAL)cam->vv[1], (REAL)cam->vv[2]);
+    C.du = SFX(mk)((REAL)cam->du[0], (REAL)cam->du[1], (REAL)cam->du[2]);
+    C.dv = SFX(mk)((REAL)cam->dv[0], (REAL)cam->dv[1], (REAL)cam->dv[2]);
+    return C;
+}
+
+/* What follows a hit, for n single rays: lane j's ray (o, d) has hit sphere hit_i[j] at root hit_t[j] on bounce k[j]
+ * of sample sid[j] of pixel pix[j].  mode 0: record_root + PackedHitRecords::finalize, four lanes a packet, then
+ * scatter (the packed modes); mode 1: hit_record_scalar, then scatter (trace_ray_scalar).  Vectors are component-major.
+ * o_out: the hit point; d_out: the scattered direction; colour_out = colour_in * attenuation, per channel.
+ * Diagnostics (each may be NULL): nrm_out, the normal against the ray; front_out; code_out, the OR_BRANCH_* code. */
+static int SFX(next_ray_n)(const or_scene* sc, uint64_t seed, uint32_t mode, size_t n, const REAL* o, const REAL* d,
+                            const int32_t* hit_i, const REAL* hit_t, const uint32_t* sid, const uint32_t* pix,
+                            const uint32_t* k, const REAL* colour_in, REAL* o_out, REAL* d_out, REAL* colour_out,
+                            REAL* nrm_out, uint8_t* front_out, uint8_t* code_out) {
+    if (!sc || mode > 1u) return 1;
+    if (n && (!o || !d || !hit_i || !hit_t || !sid || !pix || !k || !colour_in || !o_out || !d_out || !colour_out)) return 1;
+    if (sc->n_spheres && (!sc->center || !sc->radius || !sc->material || !sc->materials)) return 1;
+    for (uint32_t i = 0; i < sc->n_spheres; ++i)
+        if (sc->material[i] >= sc->n_materials) return 1;
+    for (size_t j = 0; j < n; ++j)
+        if (hit_i[j] < 0 || (uint32_t)hit_i[j] >= sc->n_spheres) return 1;
+    SFX(scene_r) S;
+    if (!SFX(scene_from)(sc, &S)) return 1;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (size_t j0 = 0; j0 < n; j0 += 4) {
+        V3 p[4], nn[4];
+        int front[4];
+        SFX(prays) R;
+        SFX(phit) H;
+        memset(&R, 0, sizeof(R));
+        memset(&H, 0, sizeof(H));
+        for (int l = 0; l < 4; ++l) {
+            const size_t j = j0 + (size_t)l < n ? j0 + (size_t)l : j0;   /* a lane past the end repeats the first */
+            const uint32_t i = (uint32_t)hit_i[j];
+            const V3 ro = SFX(mk)(o[j], o[n + j], o[2 * n + j]), rd = SFX(mk)(d[j], d[n + j], d[2 * n + j]);
+            if (mode == 1u) {
+                SFX(hit_record_scalar)(&S, ro, rd, hit_t[j], i, &p[l], &nn[l], &front[l]);
+            } else {
+                R.ox[l] = ro.x; R.oy[l] = ro.y; R.oz[l] = ro.z;
+                R.dx[l] = rd.x; R.dy[l] = rd.y; R.dz[l] = rd.z;
+                R.en[l] = 1; R.sid[l] = sid[j];
+                SFX(record_root)(&R, l, hit_t[j], S.cx[i], S.cy[i], S.cz[i], S.mat[i], &H);
+            }
+        }
+        if (mode == 0u) {
+            SFX(finalize)(&R, &H);
+            for (int l = 0; l < 4; ++l) {
+                p[l] = SFX(mk)(H.px[l], H.py[l], H.pz[l]);
+                nn[l] = SFX(mk)(H.nx[l], H.ny[l], H.nz[l]);
+                front[l] = H.front[l];
+            }
+        }
+        for (int l = 0; l < 4 && j0 + (size_t)l < n; ++l) {
+            const size_t j = j0 + (size_t)l;
+            const V3 rd = SFX(mk)(d[j], d[n + j], d[2 * n + j]);
+            V3 nd;
+            REAL att[3];
+            int code = 0;
+            SFX(scatter_dx)(&S.mats[S.mat[hit_i[j]]], rd, p[l], nn[l], front[l], pix[j], sid[j], k[j], k0, k1, &nd, att, &code);
+            o_out[j] = p[l].x; o_out[n + j] = p[l].y; o_out[2 * n + j] = p[l].z;
+            d_out[j] = nd.x; d_out[n + j] = nd.y; d_out[2 * n + j] = nd.z;
+            for (int ch = 0; ch < 3; ++ch) colour_out[(size_t)ch * n + j] = colour_in[(size_t)ch * n + j] * att[ch];
+            if (nrm_out) { nrm_out[j] = nn[l].x; nrm_out[n + j] = nn[l].y; nrm_out[2 * n + j] = nn[l].z; }
+            if (front_out) front_out[j] = (uint8_t)front[l];
+            if (code_out) code_out[j] = (uint8_t)code;
+        }
+    }
+    free(S.cx); free(S.mats);
+    return 0;
+}
+
+/* Camera::get_ray for n (col, row, pix, sid): o_out, d_out component-major. */
+static int SFX(get_ray_n)(const or_camera* cam, uint64_t seed, size_t n, const uint32_t* col, const uint32_t* row,
+                           const uint32_t* pix, const uint32_t* sid, REAL* o_out, REAL* d_out) {
+    if (!cam || cam->image_width == 0 || cam->image_height == 0) return 1;
+    if (n && (!col || !row || !pix || !sid || !o_out || !d_out)) return 1;
+    const SFX(cam_r) C = SFX(cam_from)(cam);
+    for (size_t j = 0; j < n; ++j) {
+        V3 ro, rd;
+        SFX(get_ray)(&C, col[j], row[j], pix[j], sid[j], (uint32_t)seed, (uint32_t)(seed >> 32), &ro, &rd);
+        o_out[j] = ro.x; o_out[n + j] = ro.y; o_out[2 * n + j] = ro.z;
+        d_out[j] = rd.x; d_out[n + j] = rd.y; d_out[2 * n + j] = rd.z;
+    }
     return 0;
 }

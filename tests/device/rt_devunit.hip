@@ -1,6 +1,7 @@
 // rt_devunit.hip — TEST INFRASTRUCTURE ONLY: the kernel's device math (csrc/rt_device.hpp, rt_common.hpp,
 // rt_sweep.hpp), one function per map kernel, out[i] = f(in[i]), behind a C ABI (tests/devunit_bind.py,
-// tests/test_gpu_device_math.py).  Built by `make devunit` with the product's flags into
+// tests/test_gpu_device_math.py), and two probes of whole stages on chosen lanes: the sweeps (the ray probe,
+// tests/test_gpu_cull_probe.py) and next_ray (the next-ray probe, tests/test_gpu_scatter.py).  Built by `make devunit` with the product's flags into
 // lib/librt_devunit.so; the product library never links it and it is not part of the source hash.
 //
 // Launch shape: 256-thread blocks, n a multiple of 256 (the binding pads with in-contract values), no
@@ -12,6 +13,7 @@
 #include "rt_camera.hpp"
 #include "rt_layout.hpp"
 #include "rt_host.hpp"   // the product's device tables and kernel arguments, for the ray probe
+#include "rt_launch.hpp" // frame_params: the frame half of the kernel arguments, for the next-ray probe
 
 using namespace rt;
 
@@ -88,7 +90,7 @@ __global__ void k_philox2(const uint32_t* c, const uint32_t* key, uint32_t* r, s
     r[i] = b.a; r[n + i] = b.b;
 }
 // hit_update folded over the lane's first cnt[i] (<= 8) candidates, slot-major: hb[c * n + i].
-constexpr uint32_t kSlots = 8;
+constexpr uint32_t kHitSlots = 8;
 template <typename T, bool root2, bool SCALAR>
 __global__ void k_hit(const T* hb, const T* disc, const uint32_t* idx, const uint32_t* cnt, const T* a, T* ot, int32_t* oi,
                       size_t n) {
@@ -97,7 +99,7 @@ __global__ void k_hit(const T* hb, const T* disc, const uint32_t* idx, const uin
     const T inv_a = SCALAR ? T(0) : T(1.0) / aa;   // nearest_hit
     const uint32_t m = cnt[i];
     HitBest<T> bh;
-    for (uint32_t c = 0; c < kSlots; ++c)
+    for (uint32_t c = 0; c < kHitSlots; ++c)
         if (c < m) hit_update<T, root2, SCALAR>(hb[c * n + i], disc[c * n + i], idx[c * n + i], aa, inv_a, bh);
     ot[i] = bh.bt(); oi[i] = bh.bi();
 }
@@ -222,6 +224,79 @@ int probe(const rt_scene* s, int mode, int filter_off, const T* centre, const T*
     return (int)dv.err;
 }
 
+// ---- the next-ray probe: the product's next_ray<T, SCALAR> and nothing else ----
+// Lane i: role 0 idle (the lane does not enter next_ray; its o, d, c stay as the caller left them), 1 camera
+// (cam = true: colx, rowy, pix, sid), 2 scatter (cam = false: o, d, c, hit_i, hit_t, k, pix, sid).  o, d, c are read
+// and written in place.  next_ray reads the camera, the key and the scene's centre and material tables through
+// cold_args<T>(), so the kernel takes KParams<T> by value as its first argument.
+template <typename T, bool SCALAR>
+__global__ void __launch_bounds__(kBlock) k_probe_next_ray(KParams<T> p, const uint8_t* role, const uint32_t* colx,
+                                                           const uint32_t* rowy, const uint32_t* pix, const uint32_t* sid,
+                                                           const uint32_t* k, const int32_t* hit_i, const T* hit_t, T* o,
+                                                           T* d, T* c, size_t n) {
+    const size_t i = gid();
+    const uint32_t r = role[i];
+    if (r != 0u) {
+        V3<T> ro = ld3(o, n, i), rd = ld3(d, n, i), rc = ld3(c, n, i);
+        next_ray<T, SCALAR>(r == 1u, colx[i], rowy[i], pix[i], sid[i], k[i], hit_i[i], hit_t[i], ro, rd, rc);
+        st3(o, n, i, ro);
+        st3(d, n, i, rd);
+        st3(c, n, i, rc);
+    }
+}
+
+// The kernel arguments by the product's own host steps: ProbeScene::setup for the scene half (the centre and
+// material tables of build_scene_image), frame_params for the frame half (the camera in T, rW / rH, the pinhole
+// flag, the RNG key with the fp32 fold).  mode 0: <T, false> (the packed modes), 1: <T, true> (scalar).  A scatter
+// lane's hit index must be a sphere of the scene (-1 otherwise: the kernel gathers its tables with it).
+template <typename T>
+int probe_next_ray(const rt_scene* s, const rt_camera* cam, uint64_t seed, int mode, const uint8_t* role,
+                   const uint32_t* colx, const uint32_t* rowy, const uint32_t* pix, const uint32_t* sid, const uint32_t* k,
+                   const int32_t* hit_i, const T* hit_t, T* o, T* d, T* c, size_t n) {
+    if (!s || !cam || mode < 0 || mode > 1 || n % kBlock != 0 || n > (1u << 24)) return -1;
+    if (cam->image_width == 0 || cam->image_height == 0 || s->n_spheres == 0) return -1;
+    for (size_t i = 0; i < n; ++i) {
+        if (role[i] > 2u) return -1;
+        if (role[i] == 2u && (hit_i[i] < 0 || (uint32_t)hit_i[i] >= s->n_spheres)) return -1;
+    }
+    const SceneImage im = build_scene_image(s);
+    ProbeScene<T> ps;
+    const int rc = ps.setup(im, false);
+    if (rc != RT_OK) return rc;
+    FrameArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.cam = cam;
+    fa.depth = 50u;
+    fa.spp = 16u;
+    fa.seed = seed;
+    fa.flags = mode == 1 ? RT_FLAG_MODE_SCALAR : 0u;
+    fa.rg.row_count = cam->image_height; fa.rg.row_step = 1u; fa.rg.col_count = cam->image_width;
+    frame_params(fa, ps.p);
+    const KParams<T>& p = ps.p;
+    Dev dv;
+    const uint8_t* dr = dv.in(role, n);
+    const uint32_t* dx = dv.in(colx, n);
+    const uint32_t* dy = dv.in(rowy, n);
+    const uint32_t* dp = dv.in(pix, n);
+    const uint32_t* ds = dv.in(sid, n);
+    const uint32_t* dk = dv.in(k, n);
+    const int32_t* dh = dv.in(hit_i, n);
+    const T* dt = dv.in(hit_t, n);
+    T* dor = dv.in(o, 3 * n);
+    T* dd = dv.in(d, 3 * n);
+    T* dc = dv.in(c, 3 * n);
+    if (dv.ok() && n) {
+        const dim3 g((unsigned)(n / kBlock)), b(kBlock);
+        if (mode == 0) hipLaunchKernelGGL((k_probe_next_ray<T, false>), g, b, 0, 0, p, dr, dx, dy, dp, ds, dk, dh, dt, dor, dd, dc, n);
+        else hipLaunchKernelGGL((k_probe_next_ray<T, true>), g, b, 0, 0, p, dr, dx, dy, dp, ds, dk, dh, dt, dor, dd, dc, n);
+        dv.sync();
+    }
+    dv.back(o, dor, 3 * n);
+    dv.back(d, dd, 3 * n);
+    dv.back(c, dc, 3 * n);
+    return (int)dv.err;
+}
+
 template <typename F> int run(size_t n, F&& body) {
     if (n % kBlock != 0) return -1;
     Dev d;
@@ -294,8 +369,8 @@ template <typename F> int run(size_t n, F&& body) {
                      T* t_out, int32_t* i_out, size_t n) {                                                             \
         if (mode < 0 || mode > 2) return -1;                                                                           \
         return run(n, [&](Dev& d, dim3 g, dim3 b) {                                                                    \
-            const T* dh = d.in(hb, kSlots * n); const T* dd = d.in(disc, kSlots * n);                                  \
-            const uint32_t* di = d.in(idx, kSlots * n); const uint32_t* dc = d.in(cnt, n); const T* da = d.in(a, n);   \
+            const T* dh = d.in(hb, kHitSlots * n); const T* dd = d.in(disc, kHitSlots * n);                                  \
+            const uint32_t* di = d.in(idx, kHitSlots * n); const uint32_t* dc = d.in(cnt, n); const T* da = d.in(a, n);   \
             T* ot = d.out<T>(n); int32_t* oi = d.out<int32_t>(n);                                                      \
             if (mode == 0) LAUNCH((k_hit<T, false, false>), dh, dd, di, dc, da, ot, oi, n);                            \
             else if (mode == 1) LAUNCH((k_hit<T, true, false>), dh, dd, di, dc, da, ot, oi, n);                        \
@@ -359,6 +434,18 @@ int du_probe_camera_f32(const rt_scene* s, int mode, int filter_off, const float
 int du_probe_camera_f64(const rt_scene* s, int mode, int filter_off, const double* centre, const double* d,
                         const uint8_t* active, int32_t* idx, double* t, size_t n) {
     return centre ? probe<double>(s, mode, filter_off, centre, nullptr, d, active, idx, t, n) : -1;
+}
+// The next-ray probe (above): role, colx, rowy, pix, sid, k, hit_i, hit_t: n lanes; o, d, c: [3, n] component-major, in
+// and out (an idle lane keeps the caller's values).
+int du_next_ray_f32(const rt_scene* s, const rt_camera* cam, uint64_t seed, int mode, const uint8_t* role,
+                    const uint32_t* colx, const uint32_t* rowy, const uint32_t* pix, const uint32_t* sid, const uint32_t* k,
+                    const int32_t* hit_i, const float* hit_t, float* o, float* d, float* c, size_t n) {
+    return probe_next_ray<float>(s, cam, seed, mode, role, colx, rowy, pix, sid, k, hit_i, hit_t, o, d, c, n);
+}
+int du_next_ray_f64(const rt_scene* s, const rt_camera* cam, uint64_t seed, int mode, const uint8_t* role,
+                    const uint32_t* colx, const uint32_t* rowy, const uint32_t* pix, const uint32_t* sid, const uint32_t* k,
+                    const int32_t* hit_i, const double* hit_t, double* o, double* d, double* c, size_t n) {
+    return probe_next_ray<double>(s, cam, seed, mode, role, colx, rowy, pix, sid, k, hit_i, hit_t, o, d, c, n);
 }
 // What build_scene_image makes of the scene, for the case generators (host only, no GPU): counts[8] = {n_xg, n_xs,
 // n_top, n_mg, n_gg, n_supc, n_cslots, 0}, and the first min(cap, n_cslots) words of the slot -> scene index table

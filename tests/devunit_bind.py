@@ -41,6 +41,8 @@ def load_devunit():
         for name, third in (("probe_general", vp), ("probe_camera", vp)):
             fn = getattr(lib, f"du_{name}_{sfx}")
             fn.argtypes, fn.restype = [vp, ctypes.c_int, ctypes.c_int, third, vp, vp, vp, vp, sz], ctypes.c_int
+        fn = getattr(lib, f"du_next_ray_{sfx}")
+        fn.argtypes, fn.restype = [vp, vp, u64, ctypes.c_int] + [vp] * 11 + [sz], ctypes.c_int
     lib.du_scene_layout.argtypes, lib.du_scene_layout.restype = [vp, vp, vp, sz], ctypes.c_int
     lib.du_philox4x32_10.argtypes = lib.du_philox2x32_10.argtypes = [vp, vp, vp, sz]
     lib.du_fold_key_f32.argtypes, lib.du_fold_key_f32.restype = [u64], u32
@@ -242,3 +244,26 @@ def probe_camera(flat, mode, centre, d, active, filter_off=False):
     centre = np.ascontiguousarray(centre, d.dtype)
     assert centre.shape == (3,)
     return _probe("probe_camera", flat, mode, filter_off, centre, d, active)
+
+
+# ---- the next-ray probe: the product's next_ray<T, SCALAR> on chosen lanes (tests/test_gpu_scatter.py) ----
+NEXT_RAY_MODES = {"packed": 0, "scalar": 1}
+ROLE_IDLE, ROLE_CAMERA, ROLE_SCATTER = 0, 1, 2
+
+
+def next_ray(flat, cam, seed, mode, role, colx, rowy, pix, sid, k, hit_i, hit_t, o, d, c):
+    """next_ray<T, SCALAR> per lane (n a multiple of 256; lane i of the launch holds entry i), over the kernel
+    arguments the product's host steps make of (flat, cam, seed).  role [n] u8: ROLE_IDLE (does not enter),
+    ROLE_CAMERA (colx, rowy, pix, sid), ROLE_SCATTER (o, d, c, hit_i, hit_t, k, pix, sid).  o, d, c: [3, n], float32 or
+    float64 picks the build.  Returns new (o, d, c); an idle lane's are the caller's."""
+    dt = o.dtype
+    o, d, c = (np.array(a, dtype=dt, order="C", copy=True) for a in (o, d, c))
+    n = o.shape[1]
+    assert n % BLOCK == 0 and o.shape == d.shape == c.shape == (3, n)
+    role = np.ascontiguousarray(role, np.uint8)
+    colx, rowy, pix, sid, k = (np.ascontiguousarray(a, np.uint32) for a in (colx, rowy, pix, sid, k))
+    hit_i, hit_t = np.ascontiguousarray(hit_i, np.int32), np.ascontiguousarray(hit_t, dt)
+    assert all(a.shape == (n,) for a in (role, colx, rowy, pix, sid, k, hit_i, hit_t))
+    _call("next_ray", dt, ctypes.addressof(flat.abi), ctypes.addressof(cam), seed, NEXT_RAY_MODES[mode], _p(role), _p(colx),
+          _p(rowy), _p(pix), _p(sid), _p(k), _p(hit_i), _p(hit_t), _p(o), _p(d), _p(c), n)
+    return o, d, c

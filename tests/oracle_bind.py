@@ -55,6 +55,10 @@ def load_oracle(path=None):
     for sfx in ("f64", "f32"):
         fn = getattr(lib, f"oracle_nearest_hit_{sfx}")
         fn.argtypes, fn.restype = [vp, u32, sz, vp, vp, vp, vp], ctypes.c_int
+        fn = getattr(lib, f"oracle_next_ray_{sfx}_n")
+        fn.argtypes, fn.restype = [vp, u64, u32, sz] + [vp] * 14, ctypes.c_int
+        fn = getattr(lib, f"oracle_get_ray_{sfx}_n")
+        fn.argtypes, fn.restype = [vp, u64, sz] + [vp] * 6, ctypes.c_int
     lib.oracle_fmix32.argtypes = [u32]
     lib.oracle_fmix32.restype = u32
     _libs[path] = lib
@@ -136,6 +140,43 @@ def oracle_nearest_hit(flat, mode, o, d):
                                                                        t.ctypes.data)
     assert rc == 0, rc
     return idx, t
+
+
+NEXT_RAY_MODES = {"packed": 0, "scalar": 1}
+BRANCHES = ("lambertian", "near_zero", "metal", "cannot_refract", "schlick_reflect", "refract")   # OR_BRANCH_*
+
+
+def oracle_next_ray(flat, seed, mode, o, d, hit_i, hit_t, sid, pix, k, colour):
+    """What follows a hit, per lane (oracle.h oracle_next_ray_*_n): o, d, colour [3, n] (float32 or float64 picks the
+    build), hit_i, hit_t, sid, pix, k [n].  mode: "packed" or "scalar".
+    Returns (o' [3, n], d' [3, n], colour' [3, n], normal [3, n], front [n] u8, code [n] u8: index into BRANCHES)."""
+    o = _c(o, o.dtype)
+    dt = o.dtype
+    d, colour, hit_t = _c(d, dt), _c(colour, dt), _c(hit_t, dt)
+    hit_i = _c(hit_i, np.int32)
+    sid, pix, k = (_c(a, np.uint32) for a in (sid, pix, k))
+    n = o.shape[1]
+    assert o.shape == d.shape == colour.shape == (3, n) and all(a.shape == (n,) for a in (hit_i, hit_t, sid, pix, k))
+    oo, do, co, nrm = (np.empty((3, n), dt) for _ in range(4))
+    front, code = np.empty(n, np.uint8), np.empty(n, np.uint8)
+    rc = getattr(load_oracle(), f"oracle_next_ray_{_sfx(dt)}_n")(
+        ctypes.addressof(flat.abi), seed, NEXT_RAY_MODES[mode], n, o.ctypes.data, d.ctypes.data, hit_i.ctypes.data,
+        hit_t.ctypes.data, sid.ctypes.data, pix.ctypes.data, k.ctypes.data, colour.ctypes.data, oo.ctypes.data,
+        do.ctypes.data, co.ctypes.data, nrm.ctypes.data, front.ctypes.data, code.ctypes.data)
+    assert rc == 0, rc
+    return oo, do, co, nrm, front, code
+
+
+def oracle_get_ray(dtype, cam, seed, col, row, pix, sid):
+    """Camera::get_ray per lane (cam: abi.RtCamera): (o [3, n], d [3, n]) in dtype."""
+    col, row, pix, sid = (_c(a, np.uint32) for a in (col, row, pix, sid))
+    n = col.size
+    o, d = np.empty((3, n), dtype), np.empty((3, n), dtype)
+    rc = getattr(load_oracle(), f"oracle_get_ray_{_sfx(dtype)}_n")(ctypes.addressof(cam), seed, n, col.ctypes.data,
+                                                                   row.ctypes.data, pix.ctypes.data, sid.ctypes.data,
+                                                                   o.ctypes.data, d.ctypes.data)
+    assert rc == 0, rc
+    return o, d
 
 
 def oracle_render(flat, cam, max_bounces, spp, seed, flags=0, pixels=None, precision="f64", threads=None,

@@ -17,6 +17,40 @@
 
 #include "../../oracle/oracle.h"
 
+/* The next-ray and get-ray probes (oracle_next_ray_*_n, oracle_get_ray_*_n) of the case's scene and camera on a few
+ * lanes, both modes: 7 lanes, so the last packet of four is partial; every sphere's index in turn; nothing is printed
+ * (the probes' values are tests/test_scatter_cases.py's business), a bad return code ends the run. */
+#define PROBE_LANES 7
+#define PROBE_CASE(REAL, sfx)                                                                                          \
+    static int probe_##sfx(const or_scene* sc, const or_camera* cam, uint64_t seed) {                                  \
+        enum { N = PROBE_LANES };                                                                                      \
+        REAL o[3 * N], d[3 * N], c[3 * N], t[N], oo[3 * N], dd[3 * N], co[3 * N], nrm[3 * N];                          \
+        int32_t hit[N];                                                                                                \
+        uint32_t sid[N], pix[N], k[N], col[N], row[N];                                                                 \
+        uint8_t front[N], code[N];                                                                                     \
+        int rc = 0;                                                                                                    \
+        for (int i = 0; i < N; ++i) {                                                                                  \
+            const uint32_t h = sc->n_spheres ? (uint32_t)i % sc->n_spheres : 0u;                                       \
+            hit[i] = (int32_t)h;                                                                                       \
+            for (int a = 0; a < 3; ++a) {                                                                              \
+                o[a * N + i] = (REAL)(sc->n_spheres ? sc->center[3 * h + a] : 0.0) + (REAL)(a == 1 ? 2.5 : 0.25 * i);  \
+                d[a * N + i] = (REAL)(a == 1 ? -1.0 : 0.1 * (i - 3));                                                  \
+                c[a * N + i] = (REAL)(0.25 * (a + 1));                                                                 \
+            }                                                                                                          \
+            t[i] = (REAL)(0.5 + i);                                                                                    \
+            sid[i] = (uint32_t)i; pix[i] = 1000u * (uint32_t)i; k[i] = (uint32_t)(3 * i);                              \
+            col[i] = (uint32_t)i % cam->image_width; row[i] = (uint32_t)i % cam->image_height;                         \
+        }                                                                                                              \
+        if (sc->n_spheres)                                                                                             \
+            for (uint32_t mode = 0; mode < 2; ++mode)                                                                  \
+                rc |= oracle_next_ray_##sfx##_n(sc, seed, mode, N, o, d, hit, t, sid, pix, k, c, oo, dd, co,           \
+                                                mode ? NULL : nrm, mode ? NULL : front, code);                         \
+        rc |= oracle_get_ray_##sfx##_n(cam, seed, N, col, row, pix, sid, oo, dd);                                      \
+        return rc;                                                                                                     \
+    }
+PROBE_CASE(double, f64)
+PROBE_CASE(float, f32)
+
 static void rd(const char* fmt, void* p) {
     if (scanf(fmt, p) != 1) { fprintf(stderr, "oracle_san: bad input\n"); exit(2); }
 }
@@ -61,6 +95,7 @@ int main(void) {
         else
             rc = (prec ? oracle_render_f32 : oracle_render_f64)(&sc, &cam, depth, spp, seed, flags, pix, n_pix, rgb,
                                                                   lin, &segs, (int)threads);
+        if ((prec == 1 ? probe_f32 : probe_f64)(&sc, &cam, seed) != 0) { fprintf(stderr, "oracle_san: a probe failed\n"); return 3; }
         printf("%d %" PRIu64 "\n", rc, segs);
         for (size_t i = 0; i < 3 * n_out; ++i) printf("%a\n", lin[i]);
         free(cen); free(rad); free(mat); free(mats); free(pix); free(rgb); free(lin);
