@@ -272,3 +272,45 @@ def check(lib, rc, allow=()):
     if rc != RT_OK and rc not in allow:
         raise RtError(rc, lib.rt_last_error().decode())
     return rc
+
+
+def collect(lib, ctx, stream=None, allow_range=False):
+    """rt_context_collect: wait for the work enqueued on `stream`.  Returns (RtStats, rc); rc is RT_OK, or
+    RT_ERR_RANGE (a pixel channel above 2.0) where allow_range lets that through instead of raising."""
+    st = RtStats()
+    rc = check(lib, lib.rt_context_collect(ctx, stream, ctypes.byref(st)), allow=(RT_ERR_RANGE,) if allow_range else ())
+    return st, rc
+
+
+class DeviceScope:
+    """The device allocations of one round trip on a context: `with DeviceScope(lib, ctx) as dev` frees on exit what
+    dev.alloc and dev.upload allocated, in allocation order, whether or not the body raised."""
+
+    def __init__(self, lib, ctx):
+        self.lib, self.ctx, self._owned = lib, ctx, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for ptr in self._owned:
+            self.lib.rt_device_free(self.ctx, ptr)
+        self._owned = []
+        return False
+
+    def alloc(self, nbytes):
+        ptr = ctypes.c_void_p()
+        check(self.lib, self.lib.rt_device_alloc(self.ctx, nbytes, ctypes.byref(ptr)))
+        self._owned.append(ptr)
+        return ptr
+
+    def upload(self, a):
+        """A contiguous numpy array copied into a fresh allocation."""
+        ptr = self.alloc(a.nbytes)
+        check(self.lib, self.lib.rt_memcpy_h2d(self.ctx, ptr, a.ctypes.data, a.nbytes))
+        return ptr
+
+    def download(self, ptr, a):
+        """a.nbytes from ptr into the contiguous numpy array a, which is returned."""
+        check(self.lib, self.lib.rt_memcpy_d2h(self.ctx, a.ctypes.data, ptr, a.nbytes))
+        return a

@@ -8,14 +8,19 @@
 RenderStat).  Where the reference panics (Color::to_u8_array's `<= 2.0` assert,
 color.rs:55-57; unknown material, materials.rs:31; spp == 0 -> 0/0) this raises RtError.
 There is no CPU fallback: the HIP library must be built and a GPU present.
+
+Every method checks its arguments (checks.py) before it touches the library, the context or the scene.  A method
+that reads results back does so in one abi.DeviceScope: allocate, launch, abi.collect, download.
 """
-import collections
 import ctypes
 import time
 
 import numpy as np
 
 from . import abi
+from .checks import (ADAPTIVE_PLANS, GUIDE_CHANNELS, GUIDE_NAMES, QUERY_NAMES, QUERY_OUTPUTS, Guides,  # noqa: F401
+                     _device_array, _query_shape, check_adaptive, check_guides, check_query, check_query_into,
+                     check_render_rays, check_render_rays_into, check_schedule, check_stream, split_argument)
 
 
 class RenderStat:
@@ -50,245 +55,46 @@ class Renderer:
         raise NotImplementedError
 
 
-def split_argument(samples_per_item):
-    """render_flat's samples_per_item checked: None (rt_render_async), 0 (rt_render_split_async plans) or a
-    sample count (forced)."""
-    if samples_per_item is None:
-        return None
-    if isinstance(samples_per_item, bool) or not isinstance(samples_per_item, int):
-        raise TypeError(f"samples_per_item must be None or an int, not {samples_per_item!r}")
-    if samples_per_item < 0:
-        raise ValueError(f"samples_per_item must be >= 0, not {samples_per_item}")
-    return samples_per_item
+def _flat(scene):
+    return scene.flatten() if hasattr(scene, "flatten") else scene
 
 
-def check_schedule(schedule):
-    """A progressive schedule checked before any GPU call: a non-empty, strictly increasing list of positive
-    sample counts.  Returns it as a list of ints."""
-    counts = list(schedule)
-    if not counts:
-        raise ValueError("progressive schedule is empty")
-    for n in counts:
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-            raise ValueError(f"progressive schedule entries must be ints, not {n!r}")
-    counts = [int(n) for n in counts]
-    if counts[0] < 1:
-        raise ValueError(f"progressive schedule must start at 1 sample or more, not {counts[0]}")
-    for a, b in zip(counts, counts[1:]):
-        if b <= a:
-            raise ValueError(f"progressive schedule must be strictly increasing ({a} is followed by {b})")
-    return counts
+def _abi_camera(camera):
+    return camera.abi if hasattr(camera, "abi") else camera
 
 
-ADAPTIVE_PLANS = ("host", "device")
-
-# Guide buffers (rt_render_guides_async), in the C ABI's argument order, and their channels per pixel.
-GUIDE_NAMES = ("albedo", "normal", "depth", "coverage")
-GUIDE_CHANNELS = {"albedo": 3, "normal": 3, "depth": 1, "coverage": 1}
-Guides = collections.namedtuple("Guides", GUIDE_NAMES)
+def _range(cam, tile_range=None):
+    """tile_range, or the whole image of cam."""
+    return tile_range if tile_range is not None else abi.RtTileRange(0, 1, cam.image_height, 0, cam.image_width)
 
 
-# Ray-query outputs (rt_query_hits_async), in the C ABI's argument order: name -> (components per ray, dtype; None:
-# the rays' precision).
-QUERY_NAMES = ("t", "index", "normal", "point", "front")
-QUERY_OUTPUTS = {"t": (1, None), "index": (1, np.int32), "normal": (3, None), "point": (3, None), "front": (1, np.uint8)}
+def _pointer(a, ctype):
+    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctype))
 
 
-def _query_dtype(flags):
-    return np.dtype(np.float32 if flags & abi.RT_FLAG_F32 else np.float64)
+def _render_stat(t0, cam, st, **kw):
+    """The RenderStat of a whole image of cam begun at t0, its work counters from an RtStats."""
+    return RenderStat(time.perf_counter() - t0, cam.image_width * cam.image_height, st.kernel_ms, st.samples,
+                      st.ray_segments, **kw)
 
 
-def _query_shape(name, n):
-    return (n, 3) if QUERY_OUTPUTS[name][0] == 3 else (n,)
+def _raise_range(rc):
+    if rc == abi.RT_ERR_RANGE:
+        raise abi.RtError(rc, "a pixel channel exceeded 2.0 (reference: Color::to_u8_array panics)")
 
 
-def check_query(flags, origins, directions, want=QUERY_NAMES):
-    """GpuRenderer.query's arguments checked before any GPU call: the live path's hit only (no mode flag), known
-    output names, directions (n, 3) and origins (n, 3) or (3,) of finite-or-not numbers (the library judges each
-    ray).  Returns (origins, directions, shared, want) with the arrays contiguous in the renderer's precision;
-    shared: origins has shape (3,) and is kept in float64 (the library rounds it the way it rounds a camera centre)."""
-    if flags & ~(abi.RT_FLAG_F32 | abi.RT_FLAG_ROOT2):
-        raise ValueError("ray queries are the live path's closest hit: mode 'vectorized2' only (root2 is allowed)")
-    want = tuple(want)
-    for name in want:
-        if name not in QUERY_NAMES:
-            raise ValueError(f"unknown query output {name!r} (one of {list(QUERY_NAMES)})")
-    if not want:
-        raise ValueError("no query output asked for")
-    dtype = _query_dtype(flags)
-    d = np.asarray(directions)
-    o = np.asarray(origins)
-    for what, a in (("directions", d), ("origins", o)):
-        if a.dtype.kind not in "fiu":
-            raise ValueError(f"{what} must be numbers, not dtype {a.dtype}")
-    if d.ndim != 2 or d.shape[1] != 3:
-        raise ValueError(f"directions must have shape (n, 3), not {d.shape}")
-    shared = o.shape == (3,)
-    if not shared and o.shape != d.shape:
-        raise ValueError(f"origins must have shape (3,) (one shared origin) or {d.shape} like directions, not {o.shape}")
-    if d.shape[0] > 0x7FFFFFFF:
-        raise ValueError("more than 0x7FFFFFFF rays in one query")
-    o = np.ascontiguousarray(o, dtype=np.float64 if shared else dtype)
-    return o, np.ascontiguousarray(d, dtype=dtype), shared, want
-
-
-def _device_array(obj, what, dtype, shape, device):
-    """The device pointer of obj, an object exposing __cuda_array_interface__ (a torch ROCm tensor does), after
-    checking dtype, shape, contiguity, writability where it is an output (shape given as an output's) and, where the
-    object names one (torch's .device), the device."""
-    cai = getattr(obj, "__cuda_array_interface__", None)
-    if not isinstance(cai, dict):
-        raise TypeError(f"{what} must expose __cuda_array_interface__ (a device array), not {type(obj).__name__}")
-    if np.dtype(cai["typestr"]) != np.dtype(dtype):
-        raise ValueError(f"{what} must have dtype {np.dtype(dtype).name}, not {np.dtype(cai['typestr']).name}")
-    if tuple(cai["shape"]) != tuple(shape):
-        raise ValueError(f"{what} must have shape {tuple(shape)}, not {tuple(cai['shape'])}")
-    strides = cai.get("strides")
-    if strides is not None:
-        expect, step = [], np.dtype(dtype).itemsize
-        for k in reversed(shape):
-            expect.insert(0, step)
-            step *= max(k, 1)
-        if any(s != e for s, e, k in zip(strides, expect, shape) if k > 1):
-            raise ValueError(f"{what} must be C-contiguous (strides {tuple(strides)})")
-    dev = getattr(obj, "device", None)
-    if dev is not None and hasattr(dev, "type"):
-        if dev.type != "cuda" or (dev.index is not None and dev.index != device):
-            raise ValueError(f"{what} is on {dev}, the renderer's context on device {device}")
-    ptr = cai["data"][0]
-    if not ptr and int(np.prod(shape)):
-        raise ValueError(f"{what} has a NULL data pointer")
-    return ptr
-
-
-def check_query_into(flags, device, origins, directions, outputs):
-    """GpuRenderer.query_into's arguments checked before any GPU call.  Returns (n, d_origins | None, origin | None,
-    d_directions, {name: pointer})."""
-    if flags & ~(abi.RT_FLAG_F32 | abi.RT_FLAG_ROOT2):
-        raise ValueError("ray queries are the live path's closest hit: mode 'vectorized2' only (root2 is allowed)")
-    dtype = _query_dtype(flags)
-    cai = getattr(directions, "__cuda_array_interface__", None)
-    if not isinstance(cai, dict):
-        raise TypeError(f"directions must expose __cuda_array_interface__ (a device array), not {type(directions).__name__}")
-    shape = tuple(cai["shape"])
-    if len(shape) != 2 or shape[1] != 3:
-        raise ValueError(f"directions must have shape (n, 3), not {shape}")
-    n = shape[0]
-    if n > 0x7FFFFFFF:
-        raise ValueError("more than 0x7FFFFFFF rays in one query")
-    d_dir = _device_array(directions, "directions", dtype, (n, 3), device)
-    d_org, origin = None, None
-    if hasattr(origins, "__cuda_array_interface__"):
-        d_org = _device_array(origins, "origins", dtype, (n, 3), device)
-    else:
-        origin = np.asarray(origins)
-        if origin.shape != (3,) or origin.dtype.kind not in "fiu":
-            raise ValueError("origins must be a device array of shape (n, 3) or one shared origin of 3 host numbers")
-        origin = np.ascontiguousarray(origin, dtype=np.float64)
-    ptrs = {}
-    for name, obj in outputs.items():
-        if obj is None:
-            continue
-        cw = getattr(obj, "__cuda_array_interface__", None)
-        if isinstance(cw, dict) and cw["data"][1]:
-            raise ValueError(f"{name} is read-only")
-        ptrs[name] = _device_array(obj, name, QUERY_OUTPUTS[name][1] or dtype, _query_shape(name, n), device)
-    if not ptrs:
-        raise ValueError("no query output given")
-    return n, d_org, origin, d_dir, ptrs
-
-
-def _rays_flags(flags):
-    if flags & ~(abi.RT_FLAG_F32 | abi.RT_FLAG_ROOT2):
-        raise ValueError("caller rays are rendered on the live path: mode 'vectorized2' only (root2 is allowed)")
-    return _query_dtype(flags)
-
-
-def _rays_counts(spp, n, R, pixel_base):
-    if isinstance(spp, bool) or not isinstance(spp, (int, np.integer)) or not 1 <= spp <= 1 << 20:
-        raise ValueError(f"spp must be an integer in 1..2^20, not {spp!r}")
-    if not 1 <= R <= spp:
-        raise ValueError(f"rays per pixel must be within 1..spp: directions has {R} rays per pixel, spp is {spp}")
-    if n > 0x7FFFFFFF:
-        raise ValueError("more than 0x7FFFFFFF pixels in one call")
-    if isinstance(pixel_base, bool) or not isinstance(pixel_base, (int, np.integer)) or pixel_base < 0 \
-            or pixel_base + n > 1 << 32:
-        raise ValueError(f"pixel_base must be an integer with pixel_base + n <= 2^32, not {pixel_base!r}")
-
-
-def check_render_rays(flags, spp, origins, directions, pixel_base=0):
-    """GpuRenderer.render_rays' arguments checked before any GPU call.  directions: (n, R, 3) or (n, 3) (R = 1);
-    origins: the same shape, or (3,) for one shared origin.  Returns (origins, directions (n, R, 3), shared), the arrays
-    contiguous in the renderer's precision, a shared origin kept in float64."""
-    dtype = _rays_flags(flags)
-    d = np.asarray(directions)
-    o = np.asarray(origins)
-    for what, a in (("directions", d), ("origins", o)):
-        if a.dtype.kind not in "fiu":
-            raise ValueError(f"{what} must be numbers, not dtype {a.dtype}")
-    if d.ndim not in (2, 3) or d.shape[-1] != 3:
-        raise ValueError(f"directions must have shape (n, R, 3) or (n, 3), not {d.shape}")
-    shared = o.shape == (3,)
-    if not shared and o.shape != d.shape:
-        raise ValueError(f"origins must have shape (3,) (one shared origin) or {d.shape} like directions, not {o.shape}")
-    d = d.reshape(d.shape[0], 1, 3) if d.ndim == 2 else d
-    _rays_counts(spp, d.shape[0], d.shape[1], pixel_base)
-    o = np.ascontiguousarray(o, dtype=np.float64) if shared else np.ascontiguousarray(o, dtype=dtype).reshape(d.shape)
-    return o, np.ascontiguousarray(d, dtype=dtype), shared
-
-
-def check_render_rays_into(flags, device, spp, origins, directions, rgb, linear, pixel_base=0):
-    """GpuRenderer.render_rays_into's arguments checked before any GPU call.  Returns (n, R, d_origins | None,
-    origin | None, d_directions, d_rgb | None, d_linear | None)."""
-    dtype = _rays_flags(flags)
-    cai = getattr(directions, "__cuda_array_interface__", None)
-    if not isinstance(cai, dict):
-        raise TypeError(f"directions must expose __cuda_array_interface__ (a device array), not {type(directions).__name__}")
-    shape = tuple(cai["shape"])
-    if len(shape) not in (2, 3) or shape[-1] != 3:
-        raise ValueError(f"directions must have shape (n, R, 3) or (n, 3), not {shape}")
-    n, R = shape[0], (shape[1] if len(shape) == 3 else 1)
-    _rays_counts(spp, n, R, pixel_base)
-    d_dir = _device_array(directions, "directions", dtype, shape, device)
-    d_org, origin = None, None
-    if hasattr(origins, "__cuda_array_interface__"):
-        d_org = _device_array(origins, "origins", dtype, shape, device)
-    else:
-        origin = np.asarray(origins)
-        if origin.shape != (3,) or origin.dtype.kind not in "fiu":
-            raise ValueError("origins must be a device array shaped like directions or one shared origin of 3 host numbers")
-        origin = np.ascontiguousarray(origin, dtype=np.float64)
-    ptrs = []
-    for name, obj, dt in (("rgb", rgb, np.uint8), ("linear", linear, np.float64)):
-        if obj is None:
-            ptrs.append(None)
-            continue
-        cw = getattr(obj, "__cuda_array_interface__", None)
-        if isinstance(cw, dict) and cw["data"][1]:
-            raise ValueError(f"{name} is read-only")
-        ptrs.append(_device_array(obj, name, dt, (n, 3), device))
-    if ptrs[0] is None and ptrs[1] is None:
-        raise ValueError("no output given (rgb or linear)")
-    return n, R, d_org, origin, d_dir, ptrs[0], ptrs[1]
-
-
-def check_adaptive(spp_min, spp_max, tolerance, plan="host"):
-    """GpuRenderer.adaptive's arguments checked before any GPU call: 1 <= spp_min <= spp_max, a tolerance that is
-    a number (not NaN), a plan that is "host" or "device".  Returns (spp_min, spp_max, tolerance) as
-    (int, int, float)."""
-    if plan not in ADAPTIVE_PLANS:
-        raise ValueError(f"unknown plan {plan!r} (one of {list(ADAPTIVE_PLANS)})")
-    for name, n in (("spp_min", spp_min), ("spp_max", spp_max)):
-        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
-            raise ValueError(f"{name} must be an int, not {n!r}")
-    if spp_min < 1:
-        raise ValueError(f"spp_min must be 1 or more, not {spp_min}")
-    if spp_min > spp_max:
-        raise ValueError(f"spp_min ({spp_min}) is above spp_max ({spp_max})")
-    tolerance = float(tolerance)
-    if tolerance != tolerance:
-        raise ValueError("tolerance is NaN")
-    return int(spp_min), int(spp_max), tolerance
+def _read_image(dev, n, want_linear, launch, stream=None, before_collect=None):
+    """launch(d_rgb8, d_linear) on fresh buffers of the DeviceScope dev for n pixels, then collect on `stream` and
+    read back: (rgb [n,3] u8, linear [n,3] f64 | None, RtStats, rc); rc is RT_OK or RT_ERR_RANGE."""
+    d_rgb = dev.alloc(n * 3)
+    d_lin = dev.alloc(n * 3 * 8) if want_linear else None
+    abi.check(dev.lib, launch(d_rgb, d_lin))
+    if before_collect is not None:
+        before_collect()
+    st, rc = abi.collect(dev.lib, dev.ctx, stream, allow_range=True)
+    rgb = dev.download(d_rgb, np.empty((n, 3), dtype=np.uint8))
+    lin = dev.download(d_lin, np.empty((n, 3), dtype=np.float64)) if want_linear else None
+    return rgb, lin, st, rc
 
 
 class ProgressiveSession:
@@ -303,9 +109,8 @@ class ProgressiveSession:
         self.renderer, self.lib = renderer, renderer.lib
         self.capacity = int(spp_capacity)
         self._open = False
-        if renderer._scene_flat is not flat:
-            renderer.set_scene(flat)
-        tr = tile_range if tile_range is not None else abi.RtTileRange(0, 1, cam.image_height, 0, cam.image_width)
+        renderer._use_scene(flat)
+        tr = _range(cam, tile_range)
         self.npx = tr.row_count * tr.col_count
         self._counts = np.zeros(self.npx, dtype=np.uint32)
         self._stale = False   # refine() moved counts on the device since _counts was read
@@ -329,9 +134,12 @@ class ProgressiveSession:
         return int(self._counts.min())
 
     def _refresh(self):
-        abi.check(self.lib, self.lib.rt_progressive_counts(self.renderer.ctx,
-                                                           self._counts.ctypes.data_as(ctypes.POINTER(abi.u32))))
+        abi.check(self.lib, self.lib.rt_progressive_counts(self.renderer.ctx, _pointer(self._counts, abi.u32)))
         self._stale = False
+
+    def _require_open(self):
+        if not self._open:
+            raise RuntimeError("the progressive session is closed")
 
     def _map_argument(self, counts, what):
         a = np.ascontiguousarray(counts)
@@ -339,36 +147,17 @@ class ProgressiveSession:
             raise ValueError(f"{what} must be {self.npx} unsigned sample counts, one per pixel of the session's range")
         return np.ascontiguousarray(a, dtype=np.uint32)
 
-    def _run(self, call, want_linear, image, stream):
-        """call(d_rgb8, d_linear) on fresh device buffers, then collect and read back: (rgb [n,3] u8, linear
-        [n,3] f64 | None, RtStats, rc); image=False: no buffers, returns the RtStats."""
-        if not self._open:
-            raise RuntimeError("the progressive session is closed")
+    def _run(self, launch, want_linear, image, stream):
+        """launch(d_rgb8, d_linear), the counts read again, then collect and read back: what _read_image returns;
+        image=False: no buffers, returns the RtStats."""
+        self._require_open()
         lib, ctx = self.lib, self.renderer.ctx
-        d_rgb, d_lin = ctypes.c_void_p(), ctypes.c_void_p()
-        try:
-            if image:
-                abi.check(lib, lib.rt_device_alloc(ctx, self.npx * 3, ctypes.byref(d_rgb)))
-                if want_linear:
-                    abi.check(lib, lib.rt_device_alloc(ctx, self.npx * 3 * 8, ctypes.byref(d_lin)))
-            abi.check(lib, call(d_rgb if image else None, d_lin if image and want_linear else None))
+        if not image:
+            abi.check(lib, launch(None, None))
             self._refresh()
-            st = abi.RtStats()
-            rc = abi.check(lib, lib.rt_context_collect(ctx, stream, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
-            if not image:
-                return st
-            rgb = np.empty((self.npx, 3), dtype=np.uint8)
-            abi.check(lib, lib.rt_memcpy_d2h(ctx, rgb.ctypes.data, d_rgb, self.npx * 3))
-            lin = None
-            if want_linear:
-                lin = np.empty((self.npx, 3), dtype=np.float64)
-                abi.check(lib, lib.rt_memcpy_d2h(ctx, lin.ctypes.data, d_lin, self.npx * 3 * 8))
-        finally:
-            if d_rgb:
-                lib.rt_device_free(ctx, d_rgb)
-            if d_lin:
-                lib.rt_device_free(ctx, d_lin)
-        return rgb, lin, st, rc
+            return abi.collect(lib, ctx, stream, allow_range=True)[0]
+        with abi.DeviceScope(lib, ctx) as dev:
+            return _read_image(dev, self.npx, want_linear, launch, stream, before_collect=self._refresh)
 
     def extend(self, spp_total, want_linear=False, image=True, stream=None):
         """Trace samples [done, spp_total) and reduce [0, spp_total): (rgb [n,3] u8, linear [n,3] f64 | None,
@@ -380,8 +169,7 @@ class ProgressiveSession:
     def extend_map(self, targets, want_linear=False, image=True, stream=None):
         """rt_progressive_extend_map_async: trace samples [counts[p], targets[p]) of every pixel p and reduce pixel
         p at targets[p].  Returns what extend() returns."""
-        t = self._map_argument(targets, "targets")
-        ctx, tp = self.renderer.ctx, t.ctypes.data_as(ctypes.POINTER(abi.u32))
+        ctx, tp = self.renderer.ctx, _pointer(self._map_argument(targets, "targets"), abi.u32)
         return self._run(lambda rgb, lin: self.lib.rt_progressive_extend_map_async(ctx, tp, rgb, lin, stream),
                          want_linear, image, stream)
 
@@ -389,26 +177,20 @@ class ProgressiveSession:
         """rt_progressive_snapshot_map_async: the image with pixel p at counts[p] <= its samples so far (None: at
         every pixel's own count), nothing traced.  (rgb, linear | None, RtStats, rc)."""
         c = None if counts is None else self._map_argument(counts, "counts")
-        ctx, cp = self.renderer.ctx, None if c is None else c.ctypes.data_as(ctypes.POINTER(abi.u32))
+        ctx, cp = self.renderer.ctx, _pointer(c, abi.u32)
         return self._run(lambda rgb, lin: self.lib.rt_progressive_snapshot_map_async(ctx, cp, rgb, lin, stream),
                          want_linear, True, stream)
 
     def error(self, stream=None, stats=False):
         """rt_progressive_error_async: np.float64[n], per pixel the largest channel difference between its linear
         value at counts[p] and at counts[p] // 2 samples; inf below 2 samples.  stats=True: (error, RtStats)."""
-        if not self._open:
-            raise RuntimeError("the progressive session is closed")
+        self._require_open()
         lib, ctx = self.lib, self.renderer.ctx
-        d_err = ctypes.c_void_p()
-        abi.check(lib, lib.rt_device_alloc(ctx, self.npx * 8, ctypes.byref(d_err)))
-        try:
+        with abi.DeviceScope(lib, ctx) as dev:
+            d_err = dev.alloc(self.npx * 8)
             abi.check(lib, lib.rt_progressive_error_async(ctx, d_err, stream))
-            st = abi.RtStats()
-            abi.check(lib, lib.rt_context_collect(ctx, stream, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
-            err = np.empty(self.npx, dtype=np.float64)
-            abi.check(lib, lib.rt_memcpy_d2h(ctx, err.ctypes.data, d_err, self.npx * 8))
-        finally:
-            lib.rt_device_free(ctx, d_err)
+            st, _ = abi.collect(lib, ctx, stream, allow_range=True)
+            err = dev.download(d_err, np.empty(self.npx, dtype=np.float64))
         return (err, st) if stats else err
 
     def refine(self, tolerance, spp_max, stream=None):
@@ -416,8 +198,7 @@ class ProgressiveSession:
         (n_active, n_samples): the pixels whose estimate was above `tolerance` and that went to
         min(2 * count, spp_max), and the samples enqueued for them; n_active == 0: converged, nothing traced.  The
         call waits for the selection (one small readback), not for the tracing: collect() follows."""
-        if not self._open:
-            raise RuntimeError("the progressive session is closed")
+        self._require_open()
         na, ns = abi.u64(), abi.u64()
         abi.check(self.lib, self.lib.rt_progressive_refine(self.renderer.ctx, float(tolerance), int(spp_max), stream,
                                                            ctypes.byref(na), ctypes.byref(ns)))
@@ -427,24 +208,20 @@ class ProgressiveSession:
     def refine_items(self):
         """rt_progressive_refine_items: (samples_per_item, items np.uint32[n, 4] of pixel, first, end, 0) of the
         item table the last refine() built on the device; (0, empty) when it selected nothing."""
-        if not self._open:
-            raise RuntimeError("the progressive session is closed")
-        lib, ctx, U32P = self.lib, self.renderer.ctx, ctypes.POINTER(abi.u32)
+        self._require_open()
+        lib, ctx = self.lib, self.renderer.ctx
         s, n = abi.u32(), abi.u64()
         abi.check(lib, lib.rt_progressive_refine_items(ctx, ctypes.byref(s), ctypes.byref(n), None, 0))
         items = np.zeros((n.value, 4), dtype=np.uint32)
         if n.value:
             abi.check(lib, lib.rt_progressive_refine_items(ctx, ctypes.byref(s), ctypes.byref(n),
-                                                           items.ctypes.data_as(U32P), n.value))
+                                                           _pointer(items, abi.u32), n.value))
         return s.value, items
 
     def collect(self, stream=None):
         """rt_context_collect: wait for the work enqueued on `stream` and return its RtStats (a channel above 2.0 in
         one of its reductions is not an error here)."""
-        st = abi.RtStats()
-        abi.check(self.lib, self.lib.rt_context_collect(self.renderer.ctx, stream, ctypes.byref(st)),
-                  allow=(abi.RT_ERR_RANGE,))
-        return st
+        return abi.collect(self.lib, self.renderer.ctx, stream, allow_range=True)[0]
 
     def close(self):
         if self._open:
@@ -517,68 +294,36 @@ class GpuRenderer(Renderer):
         # allocated at a freed one's address, and the render would silently use the old spheres.
         self._scene_flat = flat
 
+    def _use_scene(self, flat):
+        """Make flat the context's scene, unless it is already."""
+        if self._scene_flat is not flat:
+            self.set_scene(flat)
+
     def render_flat(self, max_bounces, spp, flat, cam, tile_range=None, want_linear=False, samples_per_item=None):
         """Render with a FlatScene / RtCamera; returns (rgb [n,3] u8, linear [n,3] f64 | None, RtStats, rc).
         samples_per_item: None = rt_render_async; 0 = rt_render_split_async with its own plan; n > 0 = that many
         samples per work item (the sample-parallel path, include/rt_mi355x.h)."""
-        lib = self.lib
         split = split_argument(samples_per_item)
-        if self._scene_flat is not flat:
-            self.set_scene(flat)
-        if tile_range is None:
-            tr = abi.RtTileRange(0, 1, cam.image_height, 0, cam.image_width)
-        else:
-            tr = tile_range
-        npx = tr.row_count * tr.col_count
-        d_rgb, d_lin = ctypes.c_void_p(), ctypes.c_void_p()
-        abi.check(lib, lib.rt_device_alloc(self.ctx, npx * 3, ctypes.byref(d_rgb)))
-        try:
-            if want_linear:
-                abi.check(lib, lib.rt_device_alloc(self.ctx, npx * 3 * 8, ctypes.byref(d_lin)))
+        self._use_scene(flat)
+        tr = _range(cam, tile_range)
+        head = (self.ctx, ctypes.byref(cam), max_bounces, spp, self.seed, self.flags, ctypes.byref(tr))
+
+        def launch(d_rgb, d_lin):
             if split is None:
-                abi.check(lib, lib.rt_render_async(self.ctx, ctypes.byref(cam), max_bounces, spp, self.seed, self.flags,
-                                                   ctypes.byref(tr), d_rgb, d_lin if want_linear else None, None))
-            else:
-                abi.check(lib, lib.rt_render_split_async(self.ctx, ctypes.byref(cam), max_bounces, spp, self.seed,
-                                                         self.flags, ctypes.byref(tr), d_rgb,
-                                                         d_lin if want_linear else None, None, split))
-            st = abi.RtStats()
-            rc = abi.check(lib, lib.rt_context_collect(self.ctx, None, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
-            rgb = np.empty((npx, 3), dtype=np.uint8)
-            abi.check(lib, lib.rt_memcpy_d2h(self.ctx, rgb.ctypes.data, d_rgb, npx * 3))
-            lin = None
-            if want_linear:
-                lin = np.empty((npx, 3), dtype=np.float64)
-                abi.check(lib, lib.rt_memcpy_d2h(self.ctx, lin.ctypes.data, d_lin, npx * 3 * 8))
-        finally:
-            lib.rt_device_free(self.ctx, d_rgb)
-            if want_linear and d_lin:
-                lib.rt_device_free(self.ctx, d_lin)
-        return rgb, lin, st, rc
+                return self.lib.rt_render_async(*head, d_rgb, d_lin, None)
+            return self.lib.rt_render_split_async(*head, d_rgb, d_lin, None, split)
+
+        with abi.DeviceScope(self.lib, self.ctx) as dev:
+            return _read_image(dev, tr.row_count * tr.col_count, want_linear, launch)
 
     def render(self, max_bounces, samples_per_pixel, scene, camera):
         t0 = time.perf_counter()
-        flat = scene.flatten() if hasattr(scene, "flatten") else scene
-        cam = camera.abi if hasattr(camera, "abi") else camera
-        rgb, _, st, rc = self.render_flat(max_bounces, samples_per_pixel, flat, cam,
+        cam = _abi_camera(camera)
+        rgb, _, st, rc = self.render_flat(max_bounces, samples_per_pixel, _flat(scene), cam,
                                           samples_per_item=0 if self.sample_parallel else None)
-        dt = time.perf_counter() - t0
-        if rc == abi.RT_ERR_RANGE:
-            raise abi.RtError(rc, "a pixel channel exceeded 2.0 (reference: Color::to_u8_array panics)")
-        img = rgb.reshape(cam.image_height, cam.image_width, 3)
-        return img, RenderStat(dt, cam.image_width * cam.image_height, st.kernel_ms, st.samples, st.ray_segments)
-
-    def _check_guides(self, want=GUIDE_NAMES):
-        """The guide calls' arguments checked before any GPU call: the live path only, known output names."""
-        if self.flags & ~abi.RT_FLAG_F32:
-            raise ValueError("guide buffers are the live path's first hits: mode 'vectorized2' without root2 only")
-        want = tuple(want)
-        for name in want:
-            if name not in GUIDE_NAMES:
-                raise ValueError(f"unknown guide buffer {name!r} (one of {list(GUIDE_NAMES)})")
-        if not want:
-            raise ValueError("no guide buffer asked for")
-        return want
+        stat = _render_stat(t0, cam, st)
+        _raise_range(rc)
+        return rgb.reshape(cam.image_height, cam.image_width, 3), stat
 
     def guides_flat(self, spp, flat, cam, tile_range=None, want=GUIDE_NAMES):
         """rt_render_guides_async with a FlatScene / RtCamera: per pixel the mean first-hit albedo, normal, depth and
@@ -586,49 +331,43 @@ class GpuRenderer(Renderer):
         definition is in include/rt_mi355x.h).  Returns ({name: float32 array, flat over the range}, RtStats, rc):
         albedo and normal [n, 3], depth and coverage [n].  want: the buffers to compute the outputs of (a value
         does not depend on which others are asked for)."""
-        want = self._check_guides(want)
-        lib = self.lib
-        if self._scene_flat is not flat:
-            self.set_scene(flat)
-        tr = tile_range if tile_range is not None else abi.RtTileRange(0, 1, cam.image_height, 0, cam.image_width)
+        want = check_guides(self.flags, want)
+        self._use_scene(flat)
+        tr = _range(cam, tile_range)
         npx = tr.row_count * tr.col_count
-        dev = {name: ctypes.c_void_p() for name in want}
-        out = {}
-        try:
-            for name in want:
-                abi.check(lib, lib.rt_device_alloc(self.ctx, npx * GUIDE_CHANNELS[name] * 4, ctypes.byref(dev[name])))
-            abi.check(lib, lib.rt_render_guides_async(self.ctx, ctypes.byref(cam), spp, self.seed, self.flags,
-                                                      ctypes.byref(tr), *[dev.get(name) for name in GUIDE_NAMES], None))
-            st = abi.RtStats()
-            rc = abi.check(lib, lib.rt_context_collect(self.ctx, None, ctypes.byref(st)))
-            for name in want:
-                ch = GUIDE_CHANNELS[name]
-                a = np.empty((npx, ch) if ch > 1 else (npx,), dtype=np.float32)
-                abi.check(lib, lib.rt_memcpy_d2h(self.ctx, a.ctypes.data, dev[name], npx * ch * 4))
-                out[name] = a
-        finally:
-            for d in dev.values():
-                if d:
-                    lib.rt_device_free(self.ctx, d)
+        shape = {name: (npx, GUIDE_CHANNELS[name]) if GUIDE_CHANNELS[name] > 1 else (npx,) for name in want}
+        with abi.DeviceScope(self.lib, self.ctx) as dev:
+            d = {name: dev.alloc(npx * GUIDE_CHANNELS[name] * 4) for name in want}
+            abi.check(self.lib, self.lib.rt_render_guides_async(self.ctx, ctypes.byref(cam), spp, self.seed, self.flags,
+                                                                ctypes.byref(tr), *[d.get(name) for name in GUIDE_NAMES],
+                                                                None))
+            st, rc = abi.collect(self.lib, self.ctx)
+            out = {name: dev.download(d[name], np.empty(shape[name], dtype=np.float32)) for name in want}
         return out, st, rc
 
     def guides(self, spp, scene, camera):
         """The guide buffers of render()'s image at `spp` samples: (Guides(albedo (H, W, 3), normal (H, W, 3),
         depth (H, W), coverage (H, W)) of float32, RenderStat).  The means are over all samples of a pixel, so
         they are premultiplied by coverage."""
-        self._check_guides()   # before any GPU call
+        check_guides(self.flags)   # before any GPU call
         t0 = time.perf_counter()
-        flat = scene.flatten() if hasattr(scene, "flatten") else scene
-        cam = camera.abi if hasattr(camera, "abi") else camera
-        out, st, _ = self.guides_flat(spp, flat, cam)
-        dt = time.perf_counter() - t0
+        cam = _abi_camera(camera)
+        out, st, _ = self.guides_flat(spp, _flat(scene), cam)
+        stat = _render_stat(t0, cam, st)
         h, w = cam.image_height, cam.image_width
-        g = Guides(out["albedo"].reshape(h, w, 3), out["normal"].reshape(h, w, 3), out["depth"].reshape(h, w),
-                   out["coverage"].reshape(h, w))
-        return g, RenderStat(dt, w * h, st.kernel_ms, st.samples, st.ray_segments)
+        return Guides(out["albedo"].reshape(h, w, 3), out["normal"].reshape(h, w, 3), out["depth"].reshape(h, w),
+                      out["coverage"].reshape(h, w)), stat
 
     def _query_flags(self, root2):
         return self.flags | (abi.RT_FLAG_ROOT2 if root2 else 0)
+
+    def _launch_query(self, n, d_org, origin, d_dir, flags, ptrs, stream):
+        return self.lib.rt_query_hits_async(self.ctx, n, d_org, _pointer(origin, abi.f64), d_dir, flags,
+                                            *[ptrs.get(name) for name in QUERY_NAMES], stream)
+
+    def _launch_rays(self, n, spp, R, d_org, origin, d_dir, max_bounces, seed, pixel_base, flags, d_rgb, d_lin, stream):
+        return self.lib.rt_render_rays_async(self.ctx, n, spp, R, d_org, _pointer(origin, abi.f64), d_dir, max_bounces,
+                                             self.seed if seed is None else seed, pixel_base, flags, d_rgb, d_lin, stream)
 
     def query(self, origins, directions, scene, root2=False, want=QUERY_NAMES):
         """rt_query_hits_async with numpy arrays: the closest hit of each ray (include/rt_mi355x.h has the
@@ -642,37 +381,19 @@ class GpuRenderer(Renderer):
         flags = self._query_flags(root2)
         o, d, shared, want = check_query(flags, origins, directions, want)   # before any GPU call
         n = d.shape[0]
-        dtype = d.dtype
-        out = {name: np.empty(_query_shape(name, n), dtype=QUERY_OUTPUTS[name][1] or dtype) for name in want}
-        flat = scene.flatten() if hasattr(scene, "flatten") else scene
-        lib = self.lib
-        if self._scene_flat is not flat:
-            self.set_scene(flat)
+        out = {name: np.empty(_query_shape(name, n), dtype=QUERY_OUTPUTS[name][1] or d.dtype) for name in want}
+        self._use_scene(_flat(scene))
         if n == 0:
             self.query_stats = abi.RtStats()
             return out
-        dev = {name: ctypes.c_void_p() for name in want}
-        d_dir, d_org = ctypes.c_void_p(), ctypes.c_void_p()
-        try:
-            abi.check(lib, lib.rt_device_alloc(self.ctx, d.nbytes, ctypes.byref(d_dir)))
-            abi.check(lib, lib.rt_memcpy_h2d(self.ctx, d_dir, d.ctypes.data, d.nbytes))
-            if not shared:
-                abi.check(lib, lib.rt_device_alloc(self.ctx, o.nbytes, ctypes.byref(d_org)))
-                abi.check(lib, lib.rt_memcpy_h2d(self.ctx, d_org, o.ctypes.data, o.nbytes))
+        with abi.DeviceScope(self.lib, self.ctx) as dev:
+            d_dir = dev.upload(d)
+            d_org = None if shared else dev.upload(o)
+            ptrs = {name: dev.alloc(out[name].nbytes) for name in want}
+            abi.check(self.lib, self._launch_query(n, d_org, o if shared else None, d_dir, flags, ptrs, None))
+            self.query_stats, _ = abi.collect(self.lib, self.ctx)
             for name in want:
-                abi.check(lib, lib.rt_device_alloc(self.ctx, out[name].nbytes, ctypes.byref(dev[name])))
-            origin = o.ctypes.data_as(ctypes.POINTER(abi.f64)) if shared else None
-            abi.check(lib, lib.rt_query_hits_async(self.ctx, n, None if shared else d_org, origin, d_dir, flags,
-                                                   *[dev.get(name) for name in QUERY_NAMES], None))
-            st = abi.RtStats()
-            abi.check(lib, lib.rt_context_collect(self.ctx, None, ctypes.byref(st)))
-            self.query_stats = st
-            for name in want:
-                abi.check(lib, lib.rt_memcpy_d2h(self.ctx, out[name].ctypes.data, dev[name], out[name].nbytes))
-        finally:
-            for p in [d_dir, d_org] + list(dev.values()):
-                if p:
-                    lib.rt_device_free(self.ctx, p)
+                dev.download(ptrs[name], out[name])
         return out
 
     def query_into(self, origins, directions, *, t=None, index=None, normal=None, point=None, front=None, stream=None,
@@ -686,13 +407,10 @@ class GpuRenderer(Renderer):
         flags = self._query_flags(root2)
         n, d_org, origin, d_dir, ptrs = check_query_into(
             flags, self.device, origins, directions, dict(t=t, index=index, normal=normal, point=point, front=front))
-        if stream is not None and (isinstance(stream, bool) or not isinstance(stream, int)):
-            raise TypeError(f"stream must be an integer stream handle or None, not {stream!r}")
+        check_stream(stream)
         if self._scene_flat is None:
             raise RuntimeError("query_into needs a scene: call set_scene first")
-        op = origin.ctypes.data_as(ctypes.POINTER(abi.f64)) if origin is not None else None
-        abi.check(self.lib, self.lib.rt_query_hits_async(self.ctx, n, d_org, op, d_dir, flags,
-                                                         *[ptrs.get(name) for name in QUERY_NAMES], stream))
+        abi.check(self.lib, self._launch_query(n, d_org, origin, d_dir, flags, ptrs, stream))
         return n
 
     def render_rays(self, max_bounces, spp, origins, directions, scene, seed=None, pixel_base=0, root2=False,
@@ -707,38 +425,15 @@ class GpuRenderer(Renderer):
         flags = self._query_flags(root2)
         o, d, shared = check_render_rays(flags, spp, origins, directions, pixel_base)   # before any GPU call
         n, R = d.shape[0], d.shape[1]
-        flat = scene.flatten() if hasattr(scene, "flatten") else scene
-        lib = self.lib
-        if self._scene_flat is not flat:
-            self.set_scene(flat)
-        rgb = np.empty((n, 3), dtype=np.uint8)
-        lin = np.empty((n, 3), dtype=np.float64) if want_linear else None
+        self._use_scene(_flat(scene))
         if n == 0:
-            return rgb, lin, abi.RtStats(), abi.RT_OK
-        d_dir, d_org, d_rgb, d_lin = (ctypes.c_void_p() for _ in range(4))
-        try:
-            abi.check(lib, lib.rt_device_alloc(self.ctx, d.nbytes, ctypes.byref(d_dir)))
-            abi.check(lib, lib.rt_memcpy_h2d(self.ctx, d_dir, d.ctypes.data, d.nbytes))
-            if not shared:
-                abi.check(lib, lib.rt_device_alloc(self.ctx, o.nbytes, ctypes.byref(d_org)))
-                abi.check(lib, lib.rt_memcpy_h2d(self.ctx, d_org, o.ctypes.data, o.nbytes))
-            abi.check(lib, lib.rt_device_alloc(self.ctx, n * 3, ctypes.byref(d_rgb)))
-            if want_linear:
-                abi.check(lib, lib.rt_device_alloc(self.ctx, n * 3 * 8, ctypes.byref(d_lin)))
-            origin = o.ctypes.data_as(ctypes.POINTER(abi.f64)) if shared else None
-            abi.check(lib, lib.rt_render_rays_async(self.ctx, n, spp, R, None if shared else d_org, origin, d_dir,
-                                                    max_bounces, self.seed if seed is None else seed, pixel_base, flags,
-                                                    d_rgb, d_lin if want_linear else None, None))
-            st = abi.RtStats()
-            rc = abi.check(lib, lib.rt_context_collect(self.ctx, None, ctypes.byref(st)), allow=(abi.RT_ERR_RANGE,))
-            abi.check(lib, lib.rt_memcpy_d2h(self.ctx, rgb.ctypes.data, d_rgb, n * 3))
-            if want_linear:
-                abi.check(lib, lib.rt_memcpy_d2h(self.ctx, lin.ctypes.data, d_lin, n * 3 * 8))
-        finally:
-            for p in (d_dir, d_org, d_rgb, d_lin):
-                if p:
-                    lib.rt_device_free(self.ctx, p)
-        return rgb, lin, st, rc
+            return (np.empty((0, 3), dtype=np.uint8), np.empty((0, 3), dtype=np.float64) if want_linear else None,
+                    abi.RtStats(), abi.RT_OK)
+        with abi.DeviceScope(self.lib, self.ctx) as dev:
+            d_dir = dev.upload(d)
+            d_org = None if shared else dev.upload(o)
+            return _read_image(dev, n, want_linear, lambda d_rgb, d_lin: self._launch_rays(
+                n, spp, R, d_org, o if shared else None, d_dir, max_bounces, seed, pixel_base, flags, d_rgb, d_lin, None))
 
     def render_rays_into(self, max_bounces, spp, origins, directions, *, rgb=None, linear=None, seed=None, pixel_base=0,
                          root2=False, stream=None):
@@ -751,23 +446,19 @@ class GpuRenderer(Renderer):
         flags = self._query_flags(root2)
         n, R, d_org, origin, d_dir, d_rgb, d_lin = check_render_rays_into(
             flags, self.device, spp, origins, directions, rgb, linear, pixel_base)
-        if stream is not None and (isinstance(stream, bool) or not isinstance(stream, int)):
-            raise TypeError(f"stream must be an integer stream handle or None, not {stream!r}")
+        check_stream(stream)
         if self._scene_flat is None:
             raise RuntimeError("render_rays_into needs a scene: call set_scene first")
-        op = origin.ctypes.data_as(ctypes.POINTER(abi.f64)) if origin is not None else None
-        abi.check(self.lib, self.lib.rt_render_rays_async(self.ctx, n, spp, R, d_org, op, d_dir, max_bounces,
-                                                          self.seed if seed is None else seed, pixel_base, flags,
-                                                          d_rgb, d_lin, stream))
+        abi.check(self.lib, self._launch_rays(n, spp, R, d_org, origin, d_dir, max_bounces, seed, pixel_base, flags,
+                                              d_rgb, d_lin, stream))
         return n
 
     def begin_progressive(self, max_bounces, spp_capacity, scene, camera, tile_range=None, max_bytes=0):
         """Open a ProgressiveSession (rt_progressive_begin) for up to spp_capacity samples per pixel.  The live
         path only: mode "vectorized2" without root2.  max_bytes: the most the record buffer may take
         (0 = the library's 24 GB budget; see rt_progressive_bytes for the cost)."""
-        flat = scene.flatten() if hasattr(scene, "flatten") else scene
-        cam = camera.abi if hasattr(camera, "abi") else camera
-        return ProgressiveSession(self, max_bounces, spp_capacity, flat, cam, tile_range, max_bytes)
+        return ProgressiveSession(self, max_bounces, spp_capacity, _flat(scene), _abi_camera(camera), tile_range,
+                                  max_bytes)
 
     def progressive(self, max_bounces, schedule, scene, camera):
         """Render at each sample count of `schedule` (strictly increasing), tracing only the new samples of
@@ -779,15 +470,13 @@ class GpuRenderer(Renderer):
         return self._progressive(max_bounces, counts, scene, camera)
 
     def _progressive(self, max_bounces, counts, scene, camera):
-        cam = camera.abi if hasattr(camera, "abi") else camera
+        cam = _abi_camera(camera)
         with self.begin_progressive(max_bounces, counts[-1], scene, cam) as session:
             for n in counts:
                 t0 = time.perf_counter()
                 rgb, _, st, rc = session.extend(n)
-                dt = time.perf_counter() - t0
-                img = rgb.reshape(cam.image_height, cam.image_width, 3)
-                yield n, img, RenderStat(dt, cam.image_width * cam.image_height, st.kernel_ms, st.samples,
-                                         st.ray_segments, range_error=rc == abi.RT_ERR_RANGE)
+                stat = _render_stat(t0, cam, st, range_error=rc == abi.RT_ERR_RANGE)
+                yield n, rgb.reshape(cam.image_height, cam.image_width, 3), stat
 
     def adaptive(self, max_bounces, spp_min, spp_max, tolerance, scene, camera, plan="host"):
         """Adaptive sampling: every pixel gets spp_min samples, then the pixels whose error estimate
@@ -799,13 +488,12 @@ class GpuRenderer(Renderer):
         back once, at the end.  Same counts, same image."""
         spp_min, spp_max, tolerance = check_adaptive(spp_min, spp_max, tolerance, plan)   # before any GPU call
         t0 = time.perf_counter()
-        cam = camera.abi if hasattr(camera, "abi") else camera
-        ms, samples, segs, iters = 0.0, 0, 0, 0
+        cam = _abi_camera(camera)
+        total = abi.RtStats()   # the work counters summed over the run
 
         def add(st):
-            nonlocal ms, samples, segs, iters
-            ms, samples, segs = ms + st.kernel_ms, samples + st.samples, segs + st.ray_segments
-            iters += st.bounce_iters
+            for field in ("kernel_ms", "samples", "ray_segments", "bounce_iters"):
+                setattr(total, field, getattr(total, field) + getattr(st, field))
 
         with self.begin_progressive(max_bounces, spp_max, scene, cam) as session:
             add(session.extend(spp_min, image=False))
@@ -825,8 +513,7 @@ class GpuRenderer(Renderer):
             rgb, _, st, rc = session.snapshot()
             add(st)
             counts = session.counts
-        dt = time.perf_counter() - t0
-        if rc == abi.RT_ERR_RANGE:
-            raise abi.RtError(rc, "a pixel channel exceeded 2.0 (reference: Color::to_u8_array panics)")
+        stat = _render_stat(t0, cam, total, bounce_iters=total.bounce_iters)
+        _raise_range(rc)
         h, w = cam.image_height, cam.image_width
-        return rgb.reshape(h, w, 3), counts.reshape(h, w), RenderStat(dt, w * h, ms, samples, segs, bounce_iters=iters)
+        return rgb.reshape(h, w, 3), counts.reshape(h, w), stat
