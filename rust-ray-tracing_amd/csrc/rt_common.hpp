@@ -72,8 +72,8 @@ template <typename T> struct KParams {
     uint32_t n_items;
     char* scratch;             // per-wave scratch regions
     size_t scratch_stride;
-    uint32_t vbytes, sbytes;   // trace_paths: position-map bytes, per-slot record bytes (PScratch)
-    uint32_t swide;            // PScratch::wide
+    uint32_t vbytes, sbytes;   // trace_paths: position-map bytes, per-slot record bytes (WaveSlots)
+    uint32_t swide;            // Records::wide
     const T* camsph;           // camera-origin table {oc, c} in the sph layout (pinhole launches)
     const float* fsph;         // filter stream: fp32 groups of 4 {cx, cy, cz, r2f} (layout above)
     const float* camf;         // camera filter table: fp32 groups of 4 {ocx, ocy, ocz, sc} (build_cam_table)
@@ -121,7 +121,7 @@ template <typename T> struct KParams {
 // j = i % nsub.  scratch / scratch_stride: finish_records' per-wave position maps.
 template <typename T> struct SParams {
     KParams<T> k;
-    char* rec;                 // record buffer: pixel x's region at x * k.sbytes (PScratch's y, c, e formats)
+    char* rec;                 // record buffer: pixel x's region at x * k.sbytes (Records' y, c, e formats)
     uint32_t S, nsub;          // samples per item, items per pixel
     uint32_t n_pix;            // pixels of the rendered set (k.n_items / nsub)
 };
@@ -223,40 +223,13 @@ template <typename T> using cptr = const __attribute__((address_space(4))) T*;
 // Cold kernel arguments (the camera) are read through an opaque pointer to the kernarg segment
 // at their point of use: otherwise the backend hoists every kernarg load to the kernel entry and
 // keeps ~40 camera SGPRs live across the whole persistent loop (SGPR spills into VGPR lanes).
-template <typename T> __device__ __forceinline__ cptr<KParams<T>> cold_args() {
-    cptr<KParams<T>> k = (cptr<KParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
+// P: the kernel's argument struct, or one it starts with (every struct above begins with KParams<T>).
+template <typename P> __device__ __forceinline__ cptr<P> cold() {
+    cptr<P> k = (cptr<P>)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));
     return k;
 }
-// The sample-parallel kernels' whole argument struct, read the same way.
-template <typename T> __device__ __forceinline__ cptr<SParams<T>> cold_split_args() {
-    cptr<SParams<T>> k = (cptr<SParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(k));
-    return k;
-}
-// ... and a progressive session's.
-template <typename T> __device__ __forceinline__ cptr<WParams<T>> cold_window_args() {
-    cptr<WParams<T>> k = (cptr<WParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(k));
-    return k;
-}
-// ... and those of its per-pixel-count kernels.
-template <typename T> __device__ __forceinline__ cptr<IParams<T>> cold_items_args() {
-    cptr<IParams<T>> k = (cptr<IParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(k));
-    return k;
-}
-template <typename T> __device__ __forceinline__ cptr<LParams<T>> cold_list_args() {
-    cptr<LParams<T>> k = (cptr<LParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(k));
-    return k;
-}
-// ... and the caller-ray kernel's.
-template <typename T> __device__ __forceinline__ cptr<RParams<T>> cold_rays_args() {
-    cptr<RParams<T>> k = (cptr<RParams<T>>)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(k));
-    return k;
-}
+template <typename T> __device__ __forceinline__ cptr<KParams<T>> cold_args() { return cold<KParams<T>>(); }
 // Same, but ordered after `dep` is computed: loads through it cannot be hoisted above that value's
 // producer (used to keep the camera constants out of SGPRs while a Philox block is in flight).
 template <typename T> __device__ __forceinline__ cptr<KParams<T>> cold_args_after(uint32_t dep) {

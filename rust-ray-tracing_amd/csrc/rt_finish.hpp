@@ -33,25 +33,40 @@ enum Mode : int {
     kModeV3 = 3,       // render_vectorized3 -> trace_vectorized3 (ray_tracing.rs:508-628): own value, swap order
 };
 
-// Per-wave scratch of trace_paths (HBM layout): the position map of the pixel being
-// reduced (P entries, u16 -- u32 past 32764 positions: the sample whose value position q holds at the
-// final read, all ones = none), then kSlots record regions indexed by sample: y[P] (T, the primary
-// ray's y), c[P] (3 T, AoS: one dwordx3 store per termination), e[P] (u8 -- u32 when depth > 254: the
-// termination bounce).  In the V1 and scalar modes c holds each sample's final value (colour x sky of
-// its own escaping ray, or 0).
+// The sample records and the position map (HBM layout).  A region holds the records of one pixel,
+// indexed by sample: y[P] (T, the primary ray's y), c[P] (3 T, AoS), e[P] (u8 -- u32 when depth > 254: the
+// termination bounce).  In the V1 and scalar modes c holds each sample's final value (colour x sky of its own
+// escaping ray, or 0).  The map (P entries, u16 -- u32 past 32764 positions) belongs to the wave that reduces a
+// pixel: the sample whose value position q holds at the final read, kNone = none.
+// A map entry is a sample index, with kWhite set when that sample hit the sky at bounce 0: its colour is white,
+// so it wrote no colour record (terminate) and the reduction reads none.  u16 entries keep the flag in bit 15
+// (P <= 32764, so no flagged index is 0xFFFF).
 template <typename T> struct C3 { T x, y, z; };
-template <typename T> struct PScratch {
-    char* base;        // wave-uniform
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kWhite = 0x80000000u;
+__device__ __forceinline__ uint32_t from16(uint32_t m) { return m == 0xFFFFu ? kNone : (m & 0x7FFFu) | ((m & 0x8000u) << 16); }
+__device__ __forceinline__ uint16_t to16(uint32_t v) { return (uint16_t)((v & 0x7FFFu) | ((v >> 16) & 0x8000u)); }
+
+// The view of the records, the same accessors over both places a region can be.  The `s` every accessor takes
+// names the region; where it starts is the only policy (region()):
+//   * WaveSlots<T> (WAVE): the per-wave scratch of trace_paths, the map and then kSlots regions; s is the wave's
+//     slot.  The offset stays in 32 bits (a wave's scratch is far below 4 GB).
+//   * PixelRegions<T>: the launch-wide record buffer of the sample-parallel path (trace_paths_split and its kin
+//     write, the finish kernels read), one region of sbytes per pixel of the rendered set, indexed by the
+//     absolute sample id; s is the pixel's index in the set and the offset is formed in 64 bits.  base: the map
+//     of the wave that reduces the pixel (the finish kernels; the trace kernels never touch it).
+// P and sbytes are the layout of a region, not the pixel's sample count: finish_pixel takes spp, P, C and s_sel
+// from the kernel arguments.  A progressive session's regions are laid out for its capacity (P = P_cap) and
+// reduced at any count up to it; wide bit 1 (the map) then follows the count, bit 0 (the width of e) the
+// session's depth.
+template <typename T, bool WAVE> struct Records {
+    char* base;        // wave-uniform: the position map (WAVE: the regions follow it, vbytes on)
+    char* rec;         // the record buffer (not WAVE)
     uint32_t P, vbytes, sbytes, wide;   // wide: bit 0 = u32 e, bit 1 = u32 map
-    static constexpr uint32_t kNone = 0xFFFFFFFFu;
-    // A map entry is a sample index, with kWhite set when that sample hit the sky at bounce 0: its
-    // colour is white, so it wrote no colour record (terminate) and the reduction reads none.  u16
-    // entries keep the flag in bit 15 (P <= 32764, so no flagged index is 0xFFFF).
-    static constexpr uint32_t kWhite = 0x80000000u;
-    __device__ __forceinline__ static uint32_t from16(uint32_t m) {
-        return m == 0xFFFFu ? kNone : (m & 0x7FFFu) | ((m & 0x8000u) << 16);
+    __device__ __forceinline__ char* region(uint32_t s) const {
+        if constexpr (WAVE) return base + vbytes + s * sbytes;
+        else return rec + (size_t)s * (size_t)sbytes;
     }
-    __device__ __forceinline__ static uint16_t to16(uint32_t v) { return (uint16_t)((v & 0x7FFFu) | ((v >> 16) & 0x8000u)); }
     __device__ __forceinline__ uint32_t map(uint32_t q) const {
         if (wide & 2u) return *(const uint32_t*)(base + 4u * q);
         return from16(*(const uint16_t*)(base + 2u * q));
@@ -60,67 +75,23 @@ template <typename T> struct PScratch {
         if (wide & 2u) *(uint32_t*)(base + 4u * q) = smp;
         else *(uint16_t*)(base + 2u * q) = to16(smp);
     }
-    __device__ __forceinline__ T& y(uint32_t s, uint32_t i) const {
-        return *(T*)(base + vbytes + s * sbytes + i * (uint32_t)sizeof(T));
-    }
-    __device__ __forceinline__ C3<T>& c(uint32_t s, uint32_t i) const {
-        return *(C3<T>*)(base + vbytes + s * sbytes + (P + 3u * i) * (uint32_t)sizeof(T));
-    }
-    __device__ __forceinline__ void store_c(uint32_t s, uint32_t i, T x, T y, T z) const {
-        T* r = &c(s, i).x;
-        r[0] = x;
-        asm volatile("" ::: "memory");   // keep the three stores apart (no dwordx3 merge)
-        r[1] = y;
-        asm volatile("" ::: "memory");
-        r[2] = z;
-    }
-    __device__ __forceinline__ uint32_t e(uint32_t s, uint32_t i) const {
-        const char* b = base + vbytes + s * sbytes + 4u * P * (uint32_t)sizeof(T);
-        return (wide & 1u) ? *(const uint32_t*)(b + 4u * i) : (uint32_t) * (const uint8_t*)(b + i);
-    }
-    __device__ __forceinline__ void set_e(uint32_t s, uint32_t i, uint32_t v) const {
-        char* b = base + vbytes + s * sbytes + 4u * P * (uint32_t)sizeof(T);
-        if (wide & 1u) *(uint32_t*)(b + 4u * i) = v;
-        else *(uint8_t*)(b + i) = (uint8_t)v;
-    }
-};
-// This wave's scratch view, re-derived from the kernel arguments where it is used (it is needed
-// only at record writes and pixel completion, so it does not hold SGPRs across the sphere sweep).
-template <typename T> __device__ __forceinline__ PScratch<T> wave_scratch(uint32_t wave) {
-    const auto& q = *cold_args<T>();
-    const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + wave;
-    return PScratch<T>{q.scratch + (size_t)gw * q.scratch_stride, q.P, q.vbytes, q.sbytes, q.swide};
-}
-
-// Record view of the sample-parallel path (trace_paths_split writes, finish_records reads): the records
-// live in a launch-wide buffer, one region of sbytes per pixel of the rendered set in PScratch's y / c / e
-// formats, indexed by the absolute sample id.  The `s` every accessor takes is the pixel's index in the
-// set (not a wave's slot) and the region's offset is formed in 64 bits.  base: the position map of the
-// wave that reduces the pixel (finish_records; the trace kernels never touch it).
-// P and sbytes are the layout of a region (y[P], c[P], e[P]), not the pixel's sample count: finish_pixel takes
-// spp, P, C and s_sel from the kernel arguments.  A progressive session's regions are laid out for its
-// capacity (P = P_cap) and reduced at any count up to it; wide bit 1 (the map) then follows the count, bit 0
-// (the width of e) the session's depth.
-template <typename T> struct RScratch {
-    char* base;        // wave-uniform
-    char* rec;
-    uint32_t P, sbytes, wide;
-    __device__ __forceinline__ uint32_t map(uint32_t q) const {
-        if (wide & 2u) return *(const uint32_t*)(base + 4u * q);
-        return PScratch<T>::from16(*(const uint16_t*)(base + 2u * q));
-    }
-    __device__ __forceinline__ void set_map(uint32_t q, uint32_t smp) const {
-        if (wide & 2u) *(uint32_t*)(base + 4u * q) = smp;
-        else *(uint16_t*)(base + 2u * q) = PScratch<T>::to16(smp);
-    }
-    __device__ __forceinline__ char* region(uint32_t s) const { return rec + (size_t)s * (size_t)sbytes; }
     __device__ __forceinline__ T& y(uint32_t s, uint32_t i) const { return *(T*)(region(s) + i * (uint32_t)sizeof(T)); }
     __device__ __forceinline__ C3<T>& c(uint32_t s, uint32_t i) const {
         return *(C3<T>*)(region(s) + (P + 3u * i) * (uint32_t)sizeof(T));
     }
+    // A termination's colour.  The wave view's three dword stores are kept apart: merged into one dwordx3 they
+    // want three consecutive VGPRs, and in trace_paths at its occupancy targets (fp32 6 waves per SIMD) the
+    // copies into them raised the register peak and spilled in the sphere sweeps.  The launch-wide view is
+    // written by the sample-parallel kernels only, which run one step lower (kWavesSplit: fp32 5): there the
+    // compiler merges the stores (one dwordx3, fp64 a dwordx4 and a dwordx2) and no kernel spills.  So the
+    // separation goes with the region policy: each family of kernels keeps the stores it was tuned with.
     __device__ __forceinline__ void store_c(uint32_t s, uint32_t i, T x, T y, T z) const {
         T* r = &c(s, i).x;
-        r[0] = x; r[1] = y; r[2] = z;
+        r[0] = x;
+        if constexpr (WAVE) asm volatile("" ::: "memory");
+        r[1] = y;
+        if constexpr (WAVE) asm volatile("" ::: "memory");
+        r[2] = z;
     }
     __device__ __forceinline__ uint32_t e(uint32_t s, uint32_t i) const {
         const char* b = region(s) + 4u * P * (uint32_t)sizeof(T);
@@ -132,15 +103,37 @@ template <typename T> struct RScratch {
         else *(uint8_t*)(b + i) = (uint8_t)v;
     }
 };
+template <typename T> using WaveSlots = Records<T, true>;
+template <typename T> using PixelRegions = Records<T, false>;
 
-// The launch's record view, from the sample-parallel kernels' arguments (no map: the trace kernels write
+// This wave's slots, re-derived from the kernel arguments where they are used (the view is needed only at
+// record writes and pixel completion, so it does not hold SGPRs across the sphere sweep).
+template <typename T> __device__ __forceinline__ WaveSlots<T> wave_scratch(uint32_t wave) {
+    const auto& q = *cold_args<T>();
+    const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + wave;
+    return WaveSlots<T>{q.scratch + (size_t)gw * q.scratch_stride, nullptr, q.P, q.vbytes, q.sbytes, q.swide};
+}
+// The launch's pixel regions, from the sample-parallel kernels' arguments (no map: the trace kernels write
 // records only).
-template <typename T> __device__ __forceinline__ RScratch<T> split_records() {
-    const auto& q = *cold_split_args<T>();
-    return RScratch<T>{nullptr, q.rec, q.k.P, q.k.sbytes, q.k.swide};
+template <typename T> __device__ __forceinline__ PixelRegions<T> split_records() {
+    const auto& q = *cold<SParams<T>>();
+    return PixelRegions<T>{nullptr, q.rec, q.k.P, 0u, q.k.sbytes, q.k.swide};
 }
 
-// PScratch sizes: the map (u16, u32 past 32764 positions), the records (e u8, u32 when depth > 254).
+// The one place that knows which view a path-loop kernel writes (rt_trace_body.hpp): the wave's slots, or SPLIT
+// the launch's pixel regions; and the region of a slot's samples in it: the slot itself, or SPLIT the slot's
+// pixel (items: the wave's row of s_item).  Functions, not lambdas of the body: a lambda there changed the
+// code of the kernels that never call it (tools/isa_diff.py).
+template <typename T, bool SPLIT> __device__ __forceinline__ Records<T, !SPLIT> trace_records(uint32_t wave) {
+    if constexpr (SPLIT) return split_records<T>();
+    else return wave_scratch<T>(wave);
+}
+template <bool SPLIT> __device__ __forceinline__ uint32_t trace_region(const uint32_t* items, uint32_t slot) {
+    if constexpr (SPLIT) return items[slot];
+    else return slot;
+}
+
+// Sizes of the views' parts: the map (u16, u32 past 32764 positions), the records (e u8, u32 when depth > 254).
 __host__ __device__ inline uint32_t paths_wide(uint32_t P, uint32_t depth) { return (depth > 254u ? 1u : 0u) | (P > 32764u ? 2u : 0u); }
 __host__ __device__ inline uint32_t paths_vbytes(uint32_t P, uint32_t wide, bool v3) {
     return v3 ? (8u * P + 255u) & ~255u   // vectorized3: slot -> sample map + the swap tables (finish_pixel)
@@ -338,18 +331,17 @@ __device__ __forceinline__ void finish_sky_direct(uint32_t item, uint32_t col, u
 // all_e0: every sample of the slot terminated at bounce 0 (trace_paths tracks it per slot).
 // The position map in LDS (live-path kernels without the mega level, P <= kLMapCap positions: config C's
 // 512 spp): the replay's scattered u16 writes, the map's initialisation and the reduction's reads stay
-// on the CU instead of going to HBM as partial lines.  Larger P uses the global map in PScratch.
-// SC: the record view, a wave's PScratch (s: its slot) or the sample-parallel path's RScratch (s: the pixel).
-template <typename T, int MODE, bool BALLOT01 = true, typename SC = PScratch<T>>
+// on the CU instead of going to HBM as partial lines.  Larger P uses the global map of the view.
+// SC: the record view, a wave's WaveSlots (s: its slot) or the sample-parallel path's PixelRegions (s: the pixel).
+template <typename T, int MODE, bool BALLOT01 = true, typename SC = WaveSlots<T>>
 __device__ __forceinline__ uint32_t finish_pixel(const SC& sc, uint32_t s, uint32_t item, uint32_t* hist,
                                                  T (*stage)[64], uint16_t* lmap, bool all_e0 = false) {
     const auto& q = *cold_args<T>();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t spp = q.spp, P = q.P, C = q.C, depth = q.depth;
-    constexpr uint32_t kNone = PScratch<T>::kNone;
     const bool lm = kLMapCap > 0u && lmap != nullptr && P <= kLMapCap;   // wave-uniform
     auto set_map = [&](uint32_t qq, uint32_t smp) {
-        if (lm) lmap[qq] = PScratch<T>::to16(smp);
+        if (lm) lmap[qq] = to16(smp);
         else sc.set_map(qq, smp);
     };
     // Bounce iterations the reference runs: K = min(depth, max e + 1).  The same pass builds the
@@ -501,7 +493,7 @@ __device__ __forceinline__ uint32_t finish_pixel(const SC& sc, uint32_t s, uint3
                     const bool U = q.s_sel == (ek & 1u);
                     const bool w_old = U && pold >= lo;
                     const bool w_new = !U || pnew < lo;
-                    const uint32_t iw = ek == 0u ? (i | PScratch<T>::kWhite) : i;
+                    const uint32_t iw = ek == 0u ? (i | kWhite) : i;
                     if (w_old || w_new) set_map(w_old ? pold : pnew, iw);
                     if (w_old && w_new) set_map(pnew, iw);
                 }
@@ -602,7 +594,7 @@ __device__ __forceinline__ uint32_t finish_pixel(const SC& sc, uint32_t s, uint3
                     const bool w_old = U && pold >= lo;   // pold, pnew < n_k <= hi (as above)
                     const bool w_new = !U || pnew < lo;
                     // At most one position except when the old one retires now and the new one later.
-                    const uint32_t iw = k == 0u ? (i | PScratch<T>::kWhite) : i;
+                    const uint32_t iw = k == 0u ? (i | kWhite) : i;
                     if (w_old || w_new) set_map(w_old ? pold : pnew, iw);
                     if (w_old && w_new) set_map(pnew, iw);
                 }
@@ -666,13 +658,13 @@ __device__ __forceinline__ uint32_t finish_pixel(const SC& sc, uint32_t s, uint3
                 vr = sk.x; vg = sk.y; vb = sk.z;
             } else if constexpr (MODE == kModeV2) {
                 uint32_t m;
-                if (lm) m = PScratch<T>::from16(lmap[qq]);
+                if (lm) m = from16(lmap[qq]);
                 else m = sc.map(qq);
                 if (m != kNone) {
                     // a bounce-0 sky hit (kWhite) wrote no record: white x sky.  Branch-free (the
                     // record slot is read anyway and replaced by white: a branch cost 0.8 % at C)
-                    const bool wh = (m & PScratch<T>::kWhite) != 0u;
-                    const C3<T> cm = sc.c(s, m & ~PScratch<T>::kWhite);
+                    const bool wh = (m & kWhite) != 0u;
+                    const C3<T> cm = sc.c(s, m & ~kWhite);
                     const V3<T> sk = sky(sc.y(s, qq));
                     vr = (wh ? T(1.0) : cm.x) * sk.x; vg = (wh ? T(1.0) : cm.y) * sk.y; vb = (wh ? T(1.0) : cm.z) * sk.z;
                 }

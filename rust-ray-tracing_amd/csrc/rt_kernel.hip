@@ -29,7 +29,7 @@
 //
 // Source layout (one translation unit): rt_experiments.hpp (build kinds), rt_formats.hpp (the formats host
 // layout and device code share; no HIP), rt_common.hpp (kernel arguments, scalar-load pipelines),
-// rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (replay + reduction),
+// rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (the record view, replay + reduction),
 // rt_trace.hpp + rt_trace_body.hpp (the persistent kernel), rt_guides.hpp (guide buffers: first hits only),
 // rt_query.hpp (ray queries: the closest hit of the caller's rays), rt_rays.hpp (full paths for the caller's
 // primary rays); rt_projection.hpp (host only: the rays of camera models the reference lacks);

@@ -470,15 +470,21 @@ static int launch_rays(LaunchContext* c, const RayArgs& a, hipStream_t st) {
     return RT_OK;
 }
 
+// The workgroups of a finish launch over n pixels whose position maps take vbytes each: four waves of one pixel
+// at a time, up to 8 workgroups per CU, their maps within the scratch budget.
+static uint64_t finish_grid(const LaunchContext* c, uint32_t n, uint32_t vbytes) {
+    const uint64_t fb = std::min<uint64_t>(((uint64_t)n + 3) / 4, (uint64_t)c->n_cu * 8u);
+    return std::max<uint64_t>(1u, std::min<uint64_t>(fb, kScratchBudget / (4ull * vbytes)));
+}
+
 // The sample-parallel kernels' arguments over (pixel, sample sub-range) items: the trace kernel writes the record
 // buffer rec (one region per pixel, p.sbytes each) and needs no scratch; the finish kernel's waves stride over
-// the pixels, each with a position map of its own in the scratch (fblocks workgroups of them).
+// the pixels, each with a position map of its own in the scratch (fblocks workgroups of them, finish_grid).
 template <typename T>
 static int split_params(LaunchContext* c, KParams<T>& p, char* rec, uint32_t S, uint32_t nsub, uint32_t n_pix,
                         hipStream_t st, SParams<T>& sp, uint64_t& fblocks) {
     p.scratch_stride = (size_t)p.vbytes;
-    fblocks = std::min<uint64_t>(((uint64_t)n_pix + 3) / 4, (uint64_t)c->n_cu * 8u);
-    fblocks = std::max<uint64_t>(1u, std::min<uint64_t>(fblocks, kScratchBudget / (4 * p.scratch_stride)));
+    fblocks = finish_grid(c, n_pix, p.vbytes);
     const int rc = ensure_bytes(c->scratch, p.scratch_stride * fblocks * 4, st);
     if (rc != RT_OK) return rc;
     p.scratch = (char*)c->scratch.p;

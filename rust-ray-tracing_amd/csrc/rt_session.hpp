@@ -117,9 +117,7 @@ static int launch_classes(LaunchContext* c, const Session& s, const std::vector<
     uint64_t need = 0;
     for (const CountClass& k : cls) {
         const uint32_t P = prog_positions(k.spp), vb = paths_vbytes(P, paths_wide(P, s.depth), false);
-        uint64_t fb = std::min<uint64_t>(((uint64_t)k.n + 3) / 4, (uint64_t)c->n_cu * 8u);
-        fb = std::max<uint64_t>(1u, std::min<uint64_t>(fb, kScratchBudget / (4ull * vb)));
-        need = std::max<uint64_t>(need, (uint64_t)vb * fb * 4u);
+        need = std::max<uint64_t>(need, (uint64_t)vb * finish_grid(c, k.n, vb) * 4u);
     }
     int rc = ensure_bytes(c->scratch, need, st);
     if (rc != RT_OK) return rc;

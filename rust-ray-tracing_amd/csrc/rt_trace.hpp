@@ -85,7 +85,7 @@ __device__ __forceinline__ bool guided_block(uint32_t np, uint32_t T, uint32_t G
 constexpr uint32_t kQCap = 128;   // camera-batch queue entries per wave (a batch adds at most 64)
 
 // SPLIT (trace_paths_split, the sample-parallel path): a work item is a (pixel, sample
-// sub-range), its records go to the launch-wide record buffer (RScratch) instead of the wave's PScratch, and
+// sub-range), its records go to the launch-wide record buffer (PixelRegions) instead of the wave's slots (WaveSlots), and
 // a completed slot is only freed: finish_records reduces every pixel in a launch of its own.
 //
 // The kernel's statements are in rt_trace_body.hpp, which each of the two kernels below includes as its
@@ -140,28 +140,40 @@ __global__ __launch_bounds__(256, W) void trace_paths_items(IParams<T> ip) {
 }
 
 // The sample-parallel path's finish: waves stride over the pixels of the set and run finish_pixel on each
-// pixel's region of the record buffer, which trace_paths_split filled in the launch before this one (the
+// pixel's region of the record buffer, which the trace kernel filled in the launch before this one (the
 // kernel boundary is the only hand-off: nothing is read that this launch's other workgroups wrote).  The
 // position map is in LDS up to kLMapCap positions, else in the wave's area of the scratch.  Each pixel's K
 // goes to the bounce-iteration counter, as trace_paths adds it.
+// The statements of the three kernels below, shared as text like rt_trace_body.hpp and for its reason: called
+// as an inlined function they compiled to the same instructions in another order (tools/isa_diff.py).  In scope:
+//   WINDOW: the regions are laid out for a session's capacity, P_cap (WParams), not for the count in the KParams
+//   LIST:   the pixels are list[0 .. n_pix) (LParams), not 0 .. n_pix
+#define RT_FINISH_BODY                                                                                              \
+    __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][64];                                                 \
+    __shared__ __attribute__((aligned(16))) T s_stage[4][3][64];                                                    \
+    __shared__ __attribute__((aligned(16))) uint16_t s_lmap[4][kLMapCap > 0u ? kLMapCap : 2];                       \
+    const uint32_t lane = threadIdx.x & 63u;                                                                        \
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                         \
+    const auto& q = *cold<SParams<T>>();                                                                            \
+    const uint32_t gw = blockIdx.x * 4u + wave, nw = gridDim.x * 4u;                                                \
+    const PixelRegions<T> sc{q.k.scratch + (size_t)gw * q.k.scratch_stride, q.rec,                                  \
+                             WINDOW ? cold<WParams<T>>()->P_cap : q.k.P, 0u, q.k.sbytes, q.k.swide};                \
+    const uint32_t n_pix = q.n_pix;                                                                                 \
+    const cptr<uint32_t> list = LIST ? (cptr<uint32_t>)cold<LParams<T>>()->list : nullptr;                          \
+    unsigned long long iters = 0;                                                                                   \
+    for (uint64_t i = gw; i < n_pix; i += nw) {                                                                     \
+        const uint32_t px = LIST ? list[i] : (uint32_t)i; /* the region and the output element are pixel px's */    \
+        iters += finish_pixel<T, kModeV2, true>(sc, px, px, s_hist[wave], s_stage[wave],                            \
+                                                kLMapCap > 0u ? s_lmap[wave] : nullptr, false);                     \
+        __builtin_amdgcn_wave_barrier();                                                                            \
+    }                                                                                                               \
+    if (lane == 0 && iters != 0ull) atomicAdd(&q.k.segs[(gw & (kSegShards - 1)) * kSegStride + 2], iters);
+
+// finish_records: every pixel of a rt_render_split_async launch, after trace_paths_split.
 template <typename T>
 __global__ __launch_bounds__(256) void finish_records(SParams<T> sp) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][64];
-    __shared__ __attribute__((aligned(16))) T s_stage[4][3][64];
-    __shared__ __attribute__((aligned(16))) uint16_t s_lmap[4][kLMapCap > 0u ? kLMapCap : 2];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const auto& q = *cold_split_args<T>();
-    const uint32_t gw = blockIdx.x * 4u + wave, nw = gridDim.x * 4u;
-    const RScratch<T> sc{q.k.scratch + (size_t)gw * q.k.scratch_stride, q.rec, q.k.P, q.k.sbytes, q.k.swide};
-    const uint32_t n_pix = q.n_pix;
-    unsigned long long iters = 0;
-    for (uint64_t px = gw; px < n_pix; px += nw) {
-        iters += finish_pixel<T, kModeV2, true>(sc, (uint32_t)px, (uint32_t)px, s_hist[wave], s_stage[wave],
-                                                kLMapCap > 0u ? s_lmap[wave] : nullptr, false);
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (lane == 0 && iters != 0ull) atomicAdd(&q.k.segs[(gw & (kSegShards - 1)) * kSegStride + 2], iters);
+    constexpr bool WINDOW = false, LIST = false;
+    RT_FINISH_BODY
 }
 
 // A session's snapshot: finish_records over the prefix [0, spp) of regions laid out for P_cap positions.  The
@@ -170,50 +182,18 @@ __global__ __launch_bounds__(256) void finish_records(SParams<T> sp) {
 // earlier, longer extend or not at all, are never read.
 template <typename T>
 __global__ __launch_bounds__(256) void finish_window(WParams<T> wp) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][64];
-    __shared__ __attribute__((aligned(16))) T s_stage[4][3][64];
-    __shared__ __attribute__((aligned(16))) uint16_t s_lmap[4][kLMapCap > 0u ? kLMapCap : 2];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const auto& q = *cold_split_args<T>();
-    const uint32_t gw = blockIdx.x * 4u + wave, nw = gridDim.x * 4u;
-    const RScratch<T> sc{q.k.scratch + (size_t)gw * q.k.scratch_stride, q.rec, cold_window_args<T>()->P_cap, q.k.sbytes,
-                         q.k.swide};
-    const uint32_t n_pix = q.n_pix;
-    unsigned long long iters = 0;
-    for (uint64_t px = gw; px < n_pix; px += nw) {
-        iters += finish_pixel<T, kModeV2, true>(sc, (uint32_t)px, (uint32_t)px, s_hist[wave], s_stage[wave],
-                                                kLMapCap > 0u ? s_lmap[wave] : nullptr, false);
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (lane == 0 && iters != 0ull) atomicAdd(&q.k.segs[(gw & (kSegShards - 1)) * kSegStride + 2], iters);
+    constexpr bool WINDOW = true, LIST = false;
+    RT_FINISH_BODY
 }
 
 // finish_window over an index list: the pixels of a session that are reduced at the same count (the counts in
-// the KParams, as finish_window reads them), one launch per distinct count of a per-pixel map.  px = list[i];
-// the region and the output element are pixel px's.
+// the KParams, as finish_window reads them), one launch per distinct count of a per-pixel map.
 template <typename T>
 __global__ __launch_bounds__(256) void finish_window_list(LParams<T> lp) {
-    __shared__ __attribute__((aligned(16))) uint32_t s_hist[4][64];
-    __shared__ __attribute__((aligned(16))) T s_stage[4][3][64];
-    __shared__ __attribute__((aligned(16))) uint16_t s_lmap[4][kLMapCap > 0u ? kLMapCap : 2];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const auto& q = *cold_split_args<T>();
-    const uint32_t gw = blockIdx.x * 4u + wave, nw = gridDim.x * 4u;
-    const RScratch<T> sc{q.k.scratch + (size_t)gw * q.k.scratch_stride, q.rec, cold_window_args<T>()->P_cap, q.k.sbytes,
-                         q.k.swide};
-    const uint32_t n_list = q.n_pix;
-    const cptr<uint32_t> list = (cptr<uint32_t>)cold_list_args<T>()->list;
-    unsigned long long iters = 0;
-    for (uint64_t i = gw; i < n_list; i += nw) {
-        const uint32_t px = list[i];
-        iters += finish_pixel<T, kModeV2, true>(sc, px, px, s_hist[wave], s_stage[wave],
-                                                kLMapCap > 0u ? s_lmap[wave] : nullptr, false);
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (lane == 0 && iters != 0ull) atomicAdd(&q.k.segs[(gw & (kSegShards - 1)) * kSegStride + 2], iters);
+    constexpr bool WINDOW = true, LIST = true;
+    RT_FINISH_BODY
 }
+#undef RT_FINISH_BODY
 
 // A session's error estimate (rt_progressive_error_async): per pixel the largest channel difference between the
 // linear snapshot at its count and at half its count, both already in device memory as doubles; +inf below 2

@@ -115,6 +115,10 @@
         return mk(r[0], r[64], r[128]);
     };
 
+    // The samples' records go through trace_records<T, SPLIT>(wave), a slot's to the region
+    // trace_region<SPLIT>(s_item[wave], slot) of it (rt_finish.hpp).  kRecY: the primary y is recorded.
+    constexpr bool kRecY = SPLIT || MODE == kModeV2;
+
     // Hand the lanes of `want` new samples in rank order, opening pixel slots as needed; returns
     // true in the lanes that got one.
     // Camera batches on the live path: pixels whose camera candidate list is empty finish at claim time
@@ -193,16 +197,16 @@
                 uint32_t sbits = (1u << (kISBusy + s)) | (CAMQ ? 1u << (kISNeed + s) : 0u);   // the slot's flags once open
                 uint32_t first = 0;
                 if constexpr (ITEMS) {   // item -> its 16-byte record {pixel, first, end}: wave-uniform scalar loads
-                    const cptr<MapItem> tab = (cptr<MapItem>)__builtin_assume_aligned(cold_items_args<T>()->items, 16);
+                    const cptr<MapItem> tab = (cptr<MapItem>)__builtin_assume_aligned(cold<IParams<T>>()->items, 16);
                     first = tab[item].first;
                     cur_end = tab[item].end;
                     item = tab[item].pixel;
                 } else if constexpr (SPLIT) {   // item -> (pixel, samples [first, cur_end))
-                    const auto& sq = *cold_split_args<T>();
+                    const auto& sq = *cold<SParams<T>>();
                     const uint32_t px = item / sq.nsub;
                     first = (item - px * sq.nsub) * sq.S;
                     if constexpr (WIN) {   // a session's window [s_begin, spp), items on the grid s_base + j S
-                        const auto& wq = *cold_window_args<T>();
+                        const auto& wq = *cold<WParams<T>>();
                         first += wq.s_base;
                         cur_end = min(spp, first + sq.S);
                         first = max(first, wq.s_begin);
@@ -212,7 +216,7 @@
                     item = px;
                 }
                 if constexpr (RAYS) {   // the caller's pixel: no camera, no image coordinates
-                    const auto& rq = *cold_rays_args<T>();
+                    const auto& rq = *cold<RParams<T>>();
                     cur_row = 0u;
                     cur_col = 0u;
                     cur_pix = rq.pixel_base + item;
@@ -274,25 +278,17 @@
     // enabled) and finish every pixel whose last sample this was.
     auto terminate = [&](bool term, bool skyhit, uint32_t e, uint32_t t_slot, uint32_t t_sid, const V3<T>& tc,
                          const V3<T>& td) {
-        if constexpr (SPLIT) {
-            if (term) {   // the same record, in the pixel's region of the record buffer
-                const RScratch<T> sc = split_records<T>();
-                const uint32_t px = s_item[wave][t_slot];
-                sc.set_e(px, t_sid, e);
-                if (skyhit && e != 0u) sc.store_c(px, t_sid, tc.x, tc.y, tc.z);
-            }
-        } else if (term) {
-            const PScratch<T> sc = wave_scratch<T>(wave);
-            sc.set_e(t_slot, t_sid, e);
+        if (term) {
+            const auto sc = trace_records<T, SPLIT>(wave);
+            const uint32_t rg = trace_region<SPLIT>(s_item[wave], t_slot);
+            sc.set_e(rg, t_sid, e);
             if (MODE == kModeV2) {
-                // three dword stores, not one dwordx3: a dwordx3 wants three consecutive VGPRs, and
-                // the copies into them raised the register peak (spills in the sphere sweeps).  A sky
-                // hit at bounce 0 is white: no record (its map entry carries kWhite, finish_pixel)
-                if (skyhit && e != 0u) sc.store_c(t_slot, t_sid, tc.x, tc.y, tc.z);
+                // A sky hit at bounce 0 is white: no record (its map entry carries kWhite, finish_pixel)
+                if (skyhit && e != 0u) sc.store_c(rg, t_sid, tc.x, tc.y, tc.z);
             } else {   // own value: colour x sky of the escaping ray's direction (:365-370 / :283-292), or black
                 V3<T> v = mk(T(0.0), T(0.0), T(0.0));
                 if (skyhit) { const V3<T> sk = sky(td.y); v = mk(tc.x * sk.x, tc.y * sk.y, tc.z * sk.z); }
-                sc.store_c(t_slot, t_sid, v.x, v.y, v.z);
+                sc.store_c(rg, t_sid, v.x, v.y, v.z);
             }
         }
         unsigned long long tm = __ballot(term);
@@ -349,9 +345,7 @@
             const V3<T> vu = mk(q.vu[0], q.vu[1], q.vu[2]), vv = mk(q.vv[0], q.vv[1], q.vv[2]);
             const V3<T> pc = add(mk(q.ulc[0], q.ulc[1], q.ulc[2]), add(mul(vu, s1), mul(vv, s2)));
             bd = unit(sub(pc, mk(q.center[0], q.center[1], q.center[2])));
-            // primary y (quirk Q2)
-            if constexpr (SPLIT) split_records<T>().y(s_item[wave][bslot], bsid) = bd.y;
-            else if (MODE == kModeV2) wave_scratch<T>(wave).y(bslot, bsid) = bd.y;
+            if (kRecY) trace_records<T, SPLIT>(wave).y(trace_region<SPLIT>(s_item[wave], bslot), bsid) = bd.y;   // primary y (quirk Q2)
         }
         T bt = T(0);
         int bi = -1;
@@ -447,7 +441,7 @@
             const uint32_t pix = (!CAMQ && fresh) ? npix : s_slotpix[wave][slot_of(ssv)];
             if constexpr (RAYS) {
                 if (fresh) {   // the caller's ray p R + s % R, as given: not normalised, colour 1
-                    const auto& rq = *cold_rays_args<T>();
+                    const auto& rq = *cold<RParams<T>>();
                     const size_t ray = (size_t)(pix - rq.pixel_base) * rq.R + sid_of(ssv) % rq.R;
                     const T* dp = rq.directions + 3 * ray;
                     d = mk(dp[0], dp[1], dp[2]);
@@ -470,12 +464,9 @@
         if (fresh) {
             k = 0;
             live = true;
-            if constexpr (SPLIT) {
+            if (kRecY) {   // primary y (quirk Q2)
                 const uint32_t ssv = ss_get();
-                split_records<T>().y(s_item[wave][slot_of(ssv)], sid_of(ssv)) = d.y;
-            } else if (MODE == kModeV2) {   // primary y (quirk Q2)
-                const uint32_t ssv = ss_get();
-                wave_scratch<T>(wave).y(slot_of(ssv), sid_of(ssv)) = d.y;
+                trace_records<T, SPLIT>(wave).y(trace_region<SPLIT>(s_item[wave], slot_of(ssv)), sid_of(ssv)) = d.y;
             }
         } else if (scat) {
             k += 1u;
