@@ -43,18 +43,26 @@ template <> __device__ __forceinline__ V3<float> dvs(V3<float> a, float s) {
     }
     return mk(a.x / s, a.y / s, a.z / s);
 }
+// sqrt, correctly rounded, of 2^-96 <= x < +inf: v_rsq_f32 (g, within 1 ulp), s = x g, and one residual step
+// s + (x - s^2) (g / 2).  s is within 2 ulp of the root, so the residual's FMA is exact, and its product with
+// g / 2 misses the true correction by under 2^-21 ulp of s: every one of the 2^31 arguments of the range
+// rounds as the library's sqrtf does (tests/test_gpu_sqrt_forms.py, exhaustive).  Five VALU ops, four of them
+// co-issuing multiplies and FMAs, against v_sqrt_f32 and the two-neighbour correction's two integer adds,
+// two compares and two selects (round 11; the forms tried: profiles/r11/sqrt_forms.txt).  Below 2^-96 the
+// residual would be subnormal; 0 and +inf give 0 x inf = NaN: not for them.
+__device__ __forceinline__ float sqrt_rg(float x) {
+    const float g = __builtin_amdgcn_rsqf(x);
+    const float s = x * g, h = 0.5f * g;
+    return __builtin_fmaf(__builtin_fmaf(-s, s, x), h, s);
+}
 // sqrt, correctly rounded, of an argument known to be +-0, >= 2^-96, +inf, <= -2^-96 or NaN (never a tiny
-// nonzero one of either sign): v_sqrt_f32 (within 1 ulp) and the compiler's own correction by the residuals of
-// the two neighbours, without its scaling for arguments below 2^-96 and its special-value select (both no-ops
-// here: 0, +inf and NaN come through the correction unchanged).  The scaling is what makes the library's
-// sqrt of a negative subnormal NaN: v_sqrt_f32 takes a subnormal input as a zero of its sign, so without it
-// sqrt(-subnormal) is -0 (tests/test_gpu_device_math.py, the exhaustive sweep).  fp64: the library sqrt.
+// nonzero one of either sign): sqrt_rg, which is NaN for negatives and NaN as it should be, and x itself for
+// +-0 and +inf (one v_cmp_class, one select).  v_rsq_f32 takes a subnormal input as a zero of its sign, so
+// without the library's scaling sqrt(+-subnormal) is not the library's value (tests/test_gpu_device_math.py,
+// the exhaustive sweep).  fp64: the library sqrt.
 __device__ __forceinline__ float sqrt_nd(float x) {
-    const float s = __builtin_amdgcn_sqrtf(x);
-    const float sdn = __int_as_float(__float_as_int(s) - 1), sup = __int_as_float(__float_as_int(s) + 1);
-    float r = __builtin_fmaf(-sdn, s, x) <= 0.0f ? sdn : s;
-    r = __builtin_fmaf(-sup, s, x) > 0.0f ? sup : r;
-    return r;
+    const float r = sqrt_rg(x);
+    return __builtin_amdgcn_classf(x, 0x260) ? x : r;   // class bits 5, 6, 9: -0, +0, +inf
 }
 __device__ __forceinline__ double sqrt_nd(double x) { return sqrt(x); }
 // fp64 a / s, s > 0, for three components: the compiler's f64 division (div_scale x2, rcp, two Newton steps,
@@ -91,12 +99,17 @@ __device__ __forceinline__ double sqrt_len(double x) {
     }
     return sqrt(x);
 }
-// fp32: sqrt_nd when no lane holds a tiny nonzero argument of either sign (a wave ballot), else the library
+// fp32: sqrt_rg when every lane's argument is in its range (a wave ballot: 2^-96 <= x < +inf), else the library
 // sqrtf -- the same correctly rounded value.  The library sequence is ~16 VALU ops, most of them single-issue (compares, selects,
 // constant operands): unit() of every camera ray, the scatter's normal length and the hit test's sqrt(disc) take
-// the short form (round 6, same-box C fp32 +1.2 %, E +0.4 %: profiles/r06/sqrt_len_nd_ab.txt).
+// the short form (round 6, same-box C fp32 +1.2 %, E +0.4 %: profiles/r06/sqrt_len_nd_ab.txt).  The ballot's two
+// compares were there before (x != 0, |x| < 2^-96); with +-0 and +inf on the library's side too, the short
+// form needs no select (round 11).  So a lane with +-0, +inf, a negative or a NaN now sends its wave to the library
+// too, with the same bits either way.  No caller passes a negative or a NaN: hit_update is reached only under
+// cand_f (rt_sweep.hpp: disc >= 0), and the other arguments are squared lengths of directions and of hit
+// normals, which are positive.  What is left is a discriminant that rounds to exactly 0 (not counted).
 __device__ __forceinline__ float sqrt_len(float x) {
-    if (__builtin_expect(__ballot(x != 0.0f && fabsf(x) < 0x1.0p-96f) == 0ull, 1)) return sqrt_nd(x);
+    if (__builtin_expect(__ballot(!(x >= 0x1.0p-96f && x < __builtin_inff())) == 0ull, 1)) return sqrt_rg(x);
     return sqrtf(x);
 }
 template <typename T> __device__ __forceinline__ V3<T> neg(V3<T> a) { return mk(-a.x, -a.y, -a.z); }
