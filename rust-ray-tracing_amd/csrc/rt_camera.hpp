@@ -457,50 +457,17 @@ __device__ __forceinline__ void next_ray(bool cam, uint32_t colx, uint32_t rowy,
     d = nd;
 }
 
-// Camera-origin sphere table for pinhole launches.  Every primary ray starts at the camera centre
-// (the host checked that the origin is the centre bit for bit), so oc = o - c and c = |oc|^2 - r^2
-// (objects.rs:252, 256; scalar: 217, 221) are the same for all of them.  Computed once per launch
-// with the same operations, in the sph group layout with {cx, cy, cz, r^2} -> {ocx, ocy, ocz, c};
-// a dummy (r^2 = -inf) gets c = +inf, so its discriminant is still -inf.
-// Also the camera filter table (fp32, groups of 4 spheres), used by the camera-batch sweep under Q1.
+// The camera tables of a launch whose primary rays all start at the camera centre O = (ox, oy, oz) (the host
+// checked that the origin is the centre bit for bit): per slot of the sweep layout a cone-cull record and the
+// camera-origin record {ocx, ocy, ocz, c}, and per cluster (then per super) a cone-cull record.  oc = O - c and
+// c = |oc|^2 - r^2 (objects.rs:252, 256; scalar: 217, 221) are the same for every such ray, so they are computed
+// once per launch with the reference's operations.  cen: the scene's AoS table {cx, cy, cz, signed radius}.
 template <typename T, bool SCALAR>
-__global__ void build_cam_table(const T* sph, T* cam, uint32_t n_slots, float* camf, uint32_t n_fslots, T ox, T oy,
-                                T oz, uint32_t pass_all, T* camx, float* cull, uint32_t n_cull, uint32_t n_real,
+__global__ void build_cam_table(const T* cen, T ox, T oy, T oz, uint32_t pass_all, T* camx, float* cull,
                                 const uint32_t* ridx, uint32_t n_cslots, const double* clus, float* cullc,
                                 uint32_t n_clp) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_slots && i >= n_fslots && i >= n_cull && i >= n_cslots && i >= n_clp) return;
-    constexpr uint32_t G = kGroup<T>, NE = 64 / sizeof(T);
-    const uint32_t g = i / G, j = i % G;
-    auto at = [&](uint32_t f) -> uint32_t {
-        return sizeof(T) == 4 ? g * NE + 8 * (j / 2) + 2 * f + (j % 2) : g * NE + 4 * j + f;
-    };
-    T ocx = T(0), ocy = T(0), ocz = T(0), c = T(INFINITY);   // slots past the exact table: dummies
-    if (i < n_slots) {
-        const T cx = sph[at(0)], cy = sph[at(1)], cz = sph[at(2)], r2 = sph[at(3)];
-        ocx = ox - cx; ocy = oy - cy; ocz = oz - cz;
-        c = SCALAR ? ((ocx * ocx + ocy * ocy) + ocz * ocz) - r2 : fma(ocz, ocz, fma(ocy, ocy, ocx * ocx)) - r2;
-        cam[at(0)] = ocx;
-        cam[at(1)] = ocy;
-        cam[at(2)] = ocz;
-        cam[at(3)] = c;
-    }
-    if (i < n_fslots) {
-        // Camera filter record (fp32 layout, nearest_hit CAMT + Q1): {ocx, ocy, ocz} in fp32 and
-        // sc = sqrt(c) - 24 u |oc| - 1e-20 rounded down (u = 2^-24), or +inf when c <= 0 (the
-        // camera is inside or on the sphere: under Q1 root1 <= 0, never a hit) or NaN.
-        const double cd = (double)c;
-        const double ocn = sqrt((double)ocx * (double)ocx + (double)ocy * (double)ocy + (double)ocz * (double)ocz);
-        float sc = pass_all ? -INFINITY : INFINITY;   // pass_all: RT_FILTER_OFF (every group exact)
-        if (cd > 0.0 && !pass_all) {
-            const double v = sqrt(cd) - 0x1.8p-20 * ocn - 1e-20;   // 24 u = 1.5 * 2^-20
-            sc = (float)v;
-            if ((double)sc > v) sc = nextafterf(sc, -INFINITY);
-        }
-        const uint32_t fg = i / 4, fj = i % 4;
-        float* out = camf + 16 * fg + 8 * (fj / 2) + (fj % 2);
-        out[0] = (float)ocx; out[2] = (float)ocy; out[4] = (float)ocz; out[6] = sc;
-    }
+    if (i >= n_cslots && i >= n_clp) return;
     // cone() (cone_walk) squares a record's w in fp32: t = w.a, p = |w x a| = sqrt(px^2 + py^2 + pz^2).  Past
     // |w| = 1.8e19 the sum is +inf, f = p cos - t sin = +inf > rp and a sphere in full view was culled (an fp64
     // render of a scene scaled by 1e19: every primary ray missed everything).  Records with |w| >= kConeWMax get
@@ -518,16 +485,13 @@ __global__ void build_cam_table(const T* sph, T* cam, uint32_t n_slots, float* c
         // rp = sqrt(r^2 (1 + 2^-20) + 64 u |w|^2) + 32 u |w| rounded up (u = 2^-24); +inf (always tested)
         // for non-finite values and under RT_FILTER_OFF, -inf for dummy slots (never pass).
         // Also the slot's camera-origin record {ocx, ocy, ocz, c} (the exact test of camera_sweep),
-        // computed with the reference's operations as above; a dummy slot gets c = +inf.
+        // computed with the reference's operations; a dummy slot gets c = +inf.
         const uint32_t sj = ridx[i];
         float w[3] = {0.0f, 0.0f, 0.0f}, rp = -INFINITY;
         T ex = T(0), ey = T(0), ez = T(0), ec = T(INFINITY);
         if (sj != 0xFFFFFFFFu) {
-            const uint32_t gj = sj / G, jj = sj % G;
-            auto atj = [&](uint32_t f) -> uint32_t {
-                return sizeof(T) == 4 ? gj * NE + 8 * (jj / 2) + 2 * f + (jj % 2) : gj * NE + 4 * jj + f;
-            };
-            const T cx = sph[atj(0)], cy = sph[atj(1)], cz = sph[atj(2)], r2 = sph[atj(3)];
+            const T cx = cen[4 * sj], cy = cen[4 * sj + 1], cz = cen[4 * sj + 2];
+            const T r2 = cen[4 * sj + 3] * cen[4 * sj + 3];   // r.powi(2) in T (objects.rs:256)
             ex = ox - cx; ey = oy - cy; ez = oz - cz;
             ec = SCALAR ? ((ex * ex + ey * ey) + ez * ez) - r2 : fma(ez, ez, fma(ey, ey, ex * ex)) - r2;
             const double wn2 = (double)ex * (double)ex + (double)ey * (double)ey + (double)ez * (double)ez;

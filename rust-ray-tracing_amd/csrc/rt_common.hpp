@@ -53,9 +53,14 @@ __device__ __forceinline__ BoxGroup load_box(const __attribute__((address_space(
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
 template <typename T> struct KParams {
-    const T* sph;              // grouped sphere records (layout above); r^2 = r.powi(2) in T (objects.rs:256)
-    const T* cen;              // [n][4] = cx, cy, cz, r^2 (AoS, finalize gather)
-    uint32_t n_groups;
+    // rsv0 .. rsv6: the places of seven members that fed the camera-origin sweep (removed with it; nothing sets
+    // or reads them: they are the zeros of context_params' memset).  They stay so that every other member keeps
+    // its kernarg offset: without them 104 of the 109 kernels other than build_cam_table compile to other code
+    // (scalar loads pair up differently, SGPR spill counts move: profiles/r12/dead_camt.txt).  Compacting the
+    // struct is a performance experiment.
+    const T* rsv0;
+    const T* cen;              // [n][4] = cx, cy, cz, signed radius (AoS: finalize gather, build_cam_table)
+    uint32_t rsv1;
     const MatT<T>* mats;       // [n] each sphere's material record, materials[material[i]] (one gather)
     uint32_t n_spheres;
     uint32_t W, H;
@@ -74,12 +79,12 @@ template <typename T> struct KParams {
     size_t scratch_stride;
     uint32_t vbytes, sbytes;   // trace_paths: position-map bytes, per-slot record bytes (WaveSlots)
     uint32_t swide;            // Records::wide
-    const T* camsph;           // camera-origin table {oc, c} in the sph layout (pinhole launches)
-    const float* fsph;         // filter stream: fp32 groups of 4 {cx, cy, cz, r2f} (layout above)
-    const float* camf;         // camera filter table: fp32 groups of 4 {ocx, ocy, ocz, sc} (build_cam_table)
-    uint32_t n_fgroups;
+    const T* rsv2;
+    const float* rsv3;
+    const float* rsv4;
+    uint32_t rsv5;
     float f_cmax, f_r2max;     // filter margin bounds: max |c|_1 and max r2f over non-exact spheres
-    float f_r2min;             // min r2f over non-exact spheres (after the host's floor)
+    float rsv6;
     float f_ir2, f_hir2, f_isr; // 1/r2min, 0.5/r2min and 8 u/sqrt(r2min), rounded up (build_scene_image)
     const float* cull;         // camera cone-cull records {wx, wy, wz, rp} per slot of the sweep layout
     const float* cullc;        // ... and per cluster, then per super (build_cam_table)
@@ -114,6 +119,9 @@ template <typename T> struct KParams {
     const uint32_t* ridx;
     uint32_t n_top, n_xg, n_xs;   // n_xs: always-exact spheres (the rest of their last group are dummies)
 };
+static_assert(sizeof(KParams<float>) == 520 && offsetof(KParams<float>, ridx) == 496 &&
+              sizeof(KParams<double>) == 592 && offsetof(KParams<double>, ridx) == 568,
+              "the kernel-argument layout the kernels were measured with (rsv0 .. rsv6 keep it)");
 
 // Arguments of the sample-parallel kernels (trace_paths_split, finish_records): KParams first, so
 // cold_args<T>() reads it from the same kernarg offsets, then what only they need.  n_items counts

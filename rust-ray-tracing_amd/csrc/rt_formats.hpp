@@ -20,7 +20,7 @@ template <typename T> struct MatT {
 //   fp32: 4 spheres per group as 2 pair-interleaved records {cx0,cx1, cy0,cy1, cz0,cz1, r0,r1}
 //         so each quantity of a sphere pair is an adjacent SGPR pair for packed-FP32 VALU ops;
 //   fp64: 2 spheres per group as {cx, cy, cz, r^2}.
-// A separate AoS table {cx, cy, cz, r^2} per sphere serves the per-lane finalize gather.
+// A separate AoS table {cx, cy, cz, signed radius} per sphere serves the per-lane finalize gather.
 // The filter stream (both precisions) is fp32 in the fp32 layout, with r^2 replaced by the filter's
 // r2f: r^2 rounded up to fp32, +inf for "always exact" spheres, -inf for dummies (see
 // general_sweep).

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256, kWavesGuide<T>) void guide_pixels(GParams<T> g
                     if (nl != 0xFFFFu) hi = camera_listed<T, false, false>(v, d, t, s_clist[wave], 1u);
                     else hi = camera_sweep<T, false, false, MEGA>(v, d, t);   // whole wave: lanes are spheres in the cull
                 } else {
-                    if (v) hi = nearest_hit<T, false, false, false, MEGA>(gp.k, o, d, t);
+                    if (v) hi = nearest_hit<T, false, false, MEGA>(o, d, t);
                 }
                 n_slots += 64u;
                 const bool hit = v && hi >= 0;

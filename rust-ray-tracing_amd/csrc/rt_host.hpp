@@ -127,8 +127,8 @@ static int stage_reserve(PinnedStage& g, size_t n) {
 // tables build_cam_table fills at a launch.  The camera tables depend only on the scene, the camera
 // centre, the scalar mode and RT_FILTER_OFF: a launch with the same key reuses them (bench frames, shards).
 template <typename T> struct DeviceScene {
-    DeviceBuffer sph, cen, fsph, rsph, rfsph, rflat, top, sup, lfs, lbx[4], clus, mats;
-    DeviceBuffer cam, camf, camx, cull, cullc;   // camera-origin, camera filter, per-sphere, cone-cull, per-cluster
+    DeviceBuffer cen, rsph, rfsph, rflat, top, sup, lfs, lbx[4], clus, mats;
+    DeviceBuffer camx, cull, cullc;   // per slot: camera-origin, cone-cull; cone-cull per cluster
     TableConsts k;
     struct CamKey { bool valid = false; double center[3] = {0, 0, 0}; uint32_t scalar = 0, off = 0; } camkey;
     void reset() { *this = DeviceScene(); }
@@ -137,14 +137,13 @@ template <typename T> static int upload_scene(DeviceScene<T>& d, const SceneTabl
     int rc = RT_OK;
     auto up = [&](DeviceBuffer& dst, const auto& v) { if (rc == RT_OK) rc = upload(dst, v); };
     auto room = [&](DeviceBuffer& dst, size_t bytes) { if (rc == RT_OK) rc = reserve(dst, bytes); };
-    up(d.sph, t.sph); up(d.cen, t.cen); up(d.fsph, t.fsph);
+    up(d.cen, t.cen);
     up(d.rsph, t.rsph); up(d.rfsph, t.rfsph); up(d.rflat, t.rflat);
     up(d.top, t.top); up(d.sup, t.sup);   // t.meg stays on the host: the mega kernels read the local levels (lbx)
     up(d.lfs, t.lfs);
     for (int lv = 0; lv < 4; ++lv) up(d.lbx[lv], t.lbx[lv]);
     up(d.clus, t.clus); up(d.mats, t.mats);
-    room(d.cam, t.cam_bytes.cam); room(d.camf, t.cam_bytes.camf); room(d.camx, t.cam_bytes.camx);
-    room(d.cull, t.cam_bytes.cull); room(d.cullc, t.cam_bytes.cullc);
+    room(d.camx, t.cam_bytes.camx); room(d.cull, t.cam_bytes.cull); room(d.cullc, t.cam_bytes.cullc);
     d.k = t.k;
     return rc;
 }
@@ -156,11 +155,7 @@ template <typename T> static int upload_scene(DeviceScene<T>& d, const SceneTabl
 template <typename T>
 static void scene_params(const DeviceScene<T>& d, const SceneCounts& n, const DeviceBuffer& ridx, const DeviceBuffer& mtiers,
                          bool filter_off, KParams<T>& p) {
-    p.sph = (const T*)d.sph.p;
     p.cen = (const T*)d.cen.p;
-    p.n_groups = d.k.n_groups;
-    p.fsph = (const float*)d.fsph.p;
-    p.n_fgroups = n.n_fgroups;
     p.rsph = (const T*)d.rsph.p;
     p.rfsph = (const float*)d.rfsph.p;
     p.ftop = (const float*)d.top.p;
@@ -185,7 +180,6 @@ static void scene_params(const DeviceScene<T>& d, const SceneCounts& n, const De
     p.n_xs = n.n_xs;
     p.f_cmax = filter_off ? std::numeric_limits<float>::infinity() : d.k.f_cmax;
     p.f_r2max = d.k.f_r2max;
-    p.f_r2min = d.k.f_r2min;
     p.f_ir2 = d.k.f_ir2;
     p.f_hir2 = d.k.f_hir2;
     p.f_isr = d.k.f_isr;
@@ -197,8 +191,6 @@ static void scene_params(const DeviceScene<T>& d, const SceneCounts& n, const De
 // of this precision.  What they hold is launch_cam_table's.
 template <typename T>
 static void cam_table_params(const DeviceScene<T>& d, const SceneCounts& n, KParams<T>& p) {
-    p.camsph = (const T*)d.cam.p;
-    p.camf = (const float*)d.camf.p;
     p.camx = (const T*)d.camx.p;
     p.cull = (const float*)d.cull.p;
     p.cullc = (const float*)d.cullc.p;
@@ -210,14 +202,11 @@ static void cam_table_params(const DeviceScene<T>& d, const SceneCounts& n, KPar
 template <typename T>
 static int launch_cam_table(const DeviceScene<T>& d, const SceneCounts& n, const DeviceBuffer& ridx, const T center[3],
                             bool scalar, bool filter_off, hipStream_t st) {
-    const uint32_t n_slots = (d.k.n_groups + 1) * kGroup<T>, n_fslots = (n.n_fgroups + 1) * 4;
-    const uint32_t n_thr = std::max(std::max(std::max(n_slots, n_fslots), n.n_cull),
-                                    std::max(n.n_cslots, n.n_clp + n.n_supc));
+    const uint32_t n_thr = std::max(n.n_cslots, n.n_clp + n.n_supc);
     auto build = scalar ? build_cam_table<T, true> : build_cam_table<T, false>;
-    hipLaunchKernelGGL(build, dim3((n_thr + 255) / 256), dim3(256), 0, st, (const T*)d.sph.p, (T*)d.cam.p, n_slots,
-                       (float*)d.camf.p, n_fslots, center[0], center[1], center[2], (uint32_t)filter_off, (T*)d.camx.p,
-                       (float*)d.cull.p, n.n_cull, n.n_spheres, (const uint32_t*)ridx.p, n.n_cslots,
-                       (const double*)d.clus.p, (float*)d.cullc.p, n.n_clp + n.n_supc);
+    hipLaunchKernelGGL(build, dim3((n_thr + 255) / 256), dim3(256), 0, st, (const T*)d.cen.p, center[0], center[1],
+                       center[2], (uint32_t)filter_off, (T*)d.camx.p, (float*)d.cull.p, (const uint32_t*)ridx.p,
+                       n.n_cslots, (const double*)d.clus.p, (float*)d.cullc.p, n.n_clp + n.n_supc);
     HIPCHK(hipGetLastError());
     return RT_OK;
 }

@@ -1,6 +1,7 @@
-// rt_layout.hpp — the scene image: every device table of a scene, built on the host (grouped sphere
-// records, filter streams, the k-d sweep layout with its box levels, group-local frames, the mega walk's
-// tier table, the camera cull's bounding spheres) and the constants the kernels take with them.
+// rt_layout.hpp — the scene image: every device table of a scene, built on the host (the AoS centre
+// table and the material records, the k-d sweep layout with its slot-order exact and filter streams and its
+// box levels, group-local frames, the mega walk's tier table, the camera cull's bounding spheres) and the
+// constants the kernels take with them.
 // build_scene_image() is the entry point; rt_context_set_scene uploads what it returns.  Plain C++, no
 // HIP: it shares rt_formats.hpp with the device code and builds with g++ alone (tests/sanitize/layout_san.cpp).
 #pragma once
@@ -24,14 +25,11 @@ static inline float round_up_f32(double v) {
     return f;
 }
 
-// Grouped, padded sphere records (layout at SphGroup) + AoS centre table, in precision T.
+// AoS centre table {cx, cy, cz, signed radius} and the material records, in precision T.  The kernels'
+// r^2 is r.powi(2) in T (objects.rs:256): cen[4 i + 3] * cen[4 i + 3], wherever a table holds it.
 template <typename T>
-static void pack_scene(const rt_scene* s, std::vector<T>& grp, std::vector<T>& cen, std::vector<MatT<T>>& mats,
-                       uint32_t& n_groups) {
-    const uint32_t G = kGroup<T>;
+static void pack_scene(const rt_scene* s, std::vector<T>& cen, std::vector<MatT<T>>& mats) {
     const uint32_t n = s->n_spheres;
-    n_groups = (n + G - 1) / G;
-    const uint32_t npad = n_groups * G;
     cen.assign((size_t)4 * (n ? n : 1), T(0));
     for (uint32_t i = 0; i < n; ++i) {
         const T r = (T)s->radius[i];
@@ -39,19 +37,6 @@ static void pack_scene(const rt_scene* s, std::vector<T>& grp, std::vector<T>& c
         cen[4 * i + 1] = (T)s->center[3 * i + 1];
         cen[4 * i + 2] = (T)s->center[3 * i + 2];
         cen[4 * i + 3] = r;       // signed radius (scalar-mode normal, objects.rs:242)
-    }
-    auto field = [&](uint32_t i, int f) -> T {   // dummies: centre 0, r^2 = -inf (never hit)
-        if (i >= n) return f == 3 ? -std::numeric_limits<T>::infinity() : T(0);
-        return f == 3 ? cen[4 * i + 3] * cen[4 * i + 3] : cen[4 * i + f];   // r.powi(2) in T (objects.rs:256)
-    };
-    grp.assign((size_t)64 / sizeof(T) * (n_groups + 1), T(0));   // + 1 dummy group: prefetch target
-    for (uint32_t i = 0; i < npad + G; ++i) {
-        const uint32_t g = i / G, j = i % G;
-        T* out = &grp[(size_t)g * (64 / sizeof(T))];
-        for (int f = 0; f < 4; ++f) {
-            if (sizeof(T) == 4) out[8 * (j / 2) + 2 * f + (j % 2)] = field(i, f);   // pair-interleaved
-            else out[4 * j + f] = field(i, f);                                     // AoS
-        }
     }
     mats.resize(s->n_materials ? s->n_materials : 1);
     for (uint32_t i = 0; i < s->n_materials; ++i) {
@@ -64,14 +49,13 @@ static void pack_scene(const rt_scene* s, std::vector<T>& grp, std::vector<T>& c
     }
 }
 
-// Filter stream for rays in precision T (layout at SphGroup, fp32, 4 spheres per group): centres
-// as the T kernel sees them, converted to fp32; r2f = the kernel's r^2 (r.powi(2) in T) rounded up
-// to fp32; +inf for "always exact" spheres; -inf for dummies.  Returns the margin bounds over the
-// other spheres: max |c|_1 (rounded up) and max r2f.
+// Filter records for rays in precision T, one fp32 {cx, cy, cz, r2f} per sphere in scene order (frec;
+// pack_sweep puts them in slot order): centres as the T kernel sees them, converted to fp32; r2f = the
+// kernel's r^2 (r.powi(2) in T) rounded up to fp32; +inf for "always exact" spheres.  Returns the margin
+// bounds over the other spheres: max |c|_1 (rounded up), max r2f and min r2f.
 template <typename T>
-static void pack_filter(const std::vector<T>& cen, uint32_t n, std::vector<float>& grp, uint32_t& n_fgroups,
-                        float& cmax, float& r2max, float& r2min, std::vector<float>& frec) {
-    n_fgroups = (n + 3) / 4;
+static void pack_filter(const std::vector<T>& cen, uint32_t n, float& cmax, float& r2max, float& r2min,
+                        std::vector<float>& frec) {
     std::vector<double> key(n);
     for (uint32_t i = 0; i < n; ++i)
         key[i] = std::fabs((double)cen[4 * i]) + std::fabs((double)cen[4 * i + 1]) + std::fabs((double)cen[4 * i + 2]) +
@@ -98,27 +82,21 @@ static void pack_filter(const std::vector<T>& cen, uint32_t n, std::vector<float
     const double floor2 = std::max(rm * 0x1.0p-10, cm * cm * 0x1.0p-16);
     double rmin = std::numeric_limits<double>::infinity();
     cm = 0.0; rm = 0.0;
-    grp.assign((size_t)16 * (n_fgroups + 1), 0.0f);
     frec.assign((size_t)4 * n, 0.0f);
-    for (uint32_t i = 0; i < 4 * (n_fgroups + 1); ++i) {
-        float f[4] = {0.0f, 0.0f, 0.0f, -std::numeric_limits<float>::infinity()};
-        if (i < n) {
-            const T r2 = cen[4 * i + 3] * cen[4 * i + 3];   // as pack_scene: r.powi(2) in T
-            f[0] = (float)cen[4 * i]; f[1] = (float)cen[4 * i + 1]; f[2] = (float)cen[4 * i + 2];
-            const double c1 = std::fabs((double)f[0]) + std::fabs((double)f[1]) + std::fabs((double)f[2]);
-            const bool finite = std::isfinite(key[i]) && std::isfinite((double)r2) && std::isfinite(c1);
-            if (!finite || key[i] > kExactRatio * median) {
-                f[3] = std::numeric_limits<float>::infinity();
-            } else {
-                f[3] = round_up_f32(std::max((double)r2, floor2));
-                cm = std::max(cm, c1);
-                rm = std::max(rm, (double)f[3]);
-                rmin = std::min(rmin, (double)f[3]);
-            }
+    for (uint32_t i = 0; i < n; ++i) {
+        float* f = &frec[(size_t)4 * i];
+        const T r2 = cen[4 * i + 3] * cen[4 * i + 3];   // r.powi(2) in T
+        f[0] = (float)cen[4 * i]; f[1] = (float)cen[4 * i + 1]; f[2] = (float)cen[4 * i + 2];
+        const double c1 = std::fabs((double)f[0]) + std::fabs((double)f[1]) + std::fabs((double)f[2]);
+        const bool finite = std::isfinite(key[i]) && std::isfinite((double)r2) && std::isfinite(c1);
+        if (!finite || key[i] > kExactRatio * median) {
+            f[3] = std::numeric_limits<float>::infinity();
+        } else {
+            f[3] = round_up_f32(std::max((double)r2, floor2));
+            cm = std::max(cm, c1);
+            rm = std::max(rm, (double)f[3]);
+            rmin = std::min(rmin, (double)f[3]);
         }
-        const uint32_t g = i / 4, j = i % 4;
-        for (int q = 0; q < 4; ++q) grp[(size_t)16 * g + 8 * (j / 2) + 2 * q + (j % 2)] = f[q];   // pair-interleaved
-        if (i < n) for (int q = 0; q < 4; ++q) frec[(size_t)4 * i + q] = f[q];
     }
     cmax = round_up_f32(cm);
     r2max = round_up_f32(rm);
@@ -254,7 +232,7 @@ static SweepLayout build_layout(const rt_scene* s) {
     return L;
 }
 
-// Slot-order streams for rays in precision T: the exact groups (SphGroup layout of pack_scene),
+// Slot-order streams for rays in precision T: the exact groups (layout at SphGroup),
 // the fp32 filter groups (pack_filter's records) and the top stream of cluster bounds: axis-aligned
 // boxes {centre C, half-extent h} in fp32, 4 per 96-byte group (BoxGroup), enclosing every member
 // with its filter radius sqrt(r2f) (so the floor applies: h >= sqrt(r2min) on every axis), h rounded
@@ -691,19 +669,17 @@ static std::vector<float> pack_flat(const std::vector<float>& rg32, size_t n_slo
 // ---- the scene image ----
 // The constants the kernels take with one precision's tables.
 struct TableConsts {
-    uint32_t n_groups = 0;                        // groups of sph
     float f_cmax = 0, f_r2max = 0, f_r2min = 0;   // the filter's margin bounds (pack_filter, pack_sweep)
     float f_ir2 = 0, f_hir2 = 0, f_isr = 0;       // 1/r2min, 0.5/r2min and 8 u/sqrt(r2min), rounded up
     float l_r2max = 0, l_r2min = 0;               // the same bounds over the cluster-local r2f (pack_local_boxes)
     float l_hir2 = 0, l_isr = 0;                  // 48 u 0.5/min and 8 u/sqrt(min), rounded up
 };
 // Bytes of the tables build_cam_table fills at a launch (allocated with the scene, never uploaded).
-struct CamTableBytes { size_t cam = 0, camf = 0, camx = 0, cull = 0, cullc = 0; };
+struct CamTableBytes { size_t camx = 0, cull = 0, cullc = 0; };
 
 // The tables of one ray precision T, as the device reads them.
 template <typename T> struct SceneTables {
-    std::vector<T> sph, cen;               // grouped sphere records; AoS centre table (pack_scene)
-    std::vector<float> fsph;               // fp32 filter stream (pack_filter)
+    std::vector<T> cen;                    // AoS centre table (pack_scene)
     std::vector<T> rsph;                   // general sweep: slot-order exact groups (pack_sweep)
     std::vector<float> rfsph;              // slot-order filter groups, inline layout (inline_stream)
     std::vector<float> rflat;              // fp32 rays: one {cx, cy, cz, r^2} record per slot (pack_flat)
@@ -720,12 +696,10 @@ template <typename T> struct SceneTables {
 // What both precisions share.
 struct SceneCounts {
     uint32_t n_spheres = 0;
-    uint32_t n_fgroups = 0;                // groups of fsph
     uint32_t n_top = 0, n_xg = 0, n_xs = 0;
     uint32_t n_mg = 0, n_gg = 0;           // mega groups (0: no mega level); giga groups (0: no giga pre-test)
     uint32_t n_cslots = 0, n_clp = 0;      // slot-order cull records; cluster records (x64)
     uint32_t n_supc = 0;                   // super records after them (x64; 0: none)
-    uint32_t n_cull = 0;                   // n_spheres rounded up to 64, + 64 padding
     float mt_lo[3] = {0, 0, 0}, mt_inv = 0;   // the grid of mtiers (pack_mega_tiers)
     uint32_t mt_n[3] = {1, 1, 1};
 };
@@ -743,11 +717,11 @@ struct SceneImage {
 // One precision's tables over the layout L.  wme (fp32 only): the world-frame mega boxes, for pack_mega_tiers.
 template <typename T>
 static void build_tables(const rt_scene* s, const SweepLayout& L, const SceneImage& im, SceneTables<T>& t,
-                         uint32_t& n_fgroups, std::vector<float>* wme) {
+                         std::vector<float>* wme) {
     std::vector<MatT<T>> mats;
     std::vector<float> frec, rf;
-    pack_scene(s, t.sph, t.cen, mats, t.k.n_groups);
-    pack_filter(t.cen, s->n_spheres, t.fsph, n_fgroups, t.k.f_cmax, t.k.f_r2max, t.k.f_r2min, frec);
+    pack_scene(s, t.cen, mats);
+    pack_filter(t.cen, s->n_spheres, t.k.f_cmax, t.k.f_r2max, t.k.f_r2min, frec);
     pack_sweep(t.cen, frec, L, t.rsph, rf, t.top, t.k.f_cmax, t.k.f_r2max, t.sup, t.meg);
     // the r^2 words of the records: fp32 rays only
     const std::vector<float>* rg32 = nullptr;
@@ -774,8 +748,6 @@ static void build_tables(const rt_scene* s, const SweepLayout& L, const SceneIma
     const double l2m = (double)k.l_r2min;
     k.l_hir2 = round_up_f32((double)kFilterMargin * 0.5 / l2m);
     k.l_isr = round_up_f32(8.0 * 0x1.0p-24 / std::sqrt(l2m));
-    t.cam_bytes.cam = t.sph.size() * sizeof(T);
-    t.cam_bytes.camf = t.fsph.size() * sizeof(float);
     t.cam_bytes.camx = (size_t)4 * im.n.n_cslots * sizeof(T);
     t.cam_bytes.cull = (size_t)4 * im.n.n_cslots * sizeof(float);
     t.cam_bytes.cullc = t.clus.size() / 4 * 4 * sizeof(float);
@@ -795,13 +767,11 @@ static SceneImage build_scene_image(const rt_scene* s) {
     im.n.n_cslots = 4u * L.n_xg + 16u * ncl + 64u;
     im.n.n_clp = (ncl + 63u) / 64u * 64u;
     im.n.n_supc = ncl > 128u ? (ncl / 4u + 63u) / 64u * 64u : 0u;
-    im.n.n_cull = (s->n_spheres + 63u) / 64u * 64u + 64u;
     im.ridx.assign(im.n.n_cslots, 0xFFFFFFFFu);
     for (size_t i = 0; i < L.slot.size(); ++i) if (L.slot[i] >= 0) im.ridx[i] = (uint32_t)L.slot[i];
-    uint32_t nf64 = 0;   // n_fgroups is the fp32 call's (the same count)
     std::vector<float> wme;
-    build_tables(s, L, im, im.t64, nf64, nullptr);
-    build_tables(s, L, im, im.t32, im.n.n_fgroups, &wme);
+    build_tables(s, L, im, im.t64, nullptr);
+    build_tables(s, L, im, im.t32, &wme);
     im.n.n_mg = im.t32.meg.empty() ? 0u : (uint32_t)(im.t32.meg.size() / kBoxFloats - 1);   // groups, without the empty one
     if (im.n.n_mg) {
         im.n.n_gg = L.giga && im.n.n_mg <= 16u ? (im.n.n_mg + 3u) / 4u : 0u;

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, kWavesQuery<T>) void query_rays(QParams<T> qp)
             if constexpr (SHARED) {
                 hi = camera_sweep<T, ROOT2, false, MEGA>(v, d, t);   // whole wave: lanes are spheres in the cull
             } else {
-                if (v) hi = nearest_hit<T, ROOT2, false, false, MEGA>(qp.k, o, d, t);
+                if (v) hi = nearest_hit<T, ROOT2, false, MEGA>(o, d, t);
             }
             n_slots += 64u;
             n_seg += (unsigned long long)__builtin_popcountll(vm);

@@ -65,7 +65,6 @@ __global__ __launch_bounds__(256, W) void trace_paths_rays(RParams<T> rp) {
     constexpr bool SPLIT = kSplitKernel<T, false>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, false>;
     constexpr bool RAYS = kSplitKernel<T, true>, CAMQ = false;
     constexpr int MODE = kModeV2;
-    const KParams<T>& p = rp.k;
 #include "rt_trace_body.hpp"
 }
 

@@ -110,7 +110,6 @@ __global__ __launch_bounds__(256, W) void trace_paths_split(SParams<T> sp) {
     constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, false>, ROOT2 = false;
     constexpr bool RAYS = kSplitKernel<T, false>;
     constexpr int MODE = kModeV2;
-    const KParams<T>& p = sp.k;
 #include "rt_trace_body.hpp"
 }
 
@@ -122,7 +121,6 @@ __global__ __launch_bounds__(256, W) void trace_paths_window(WParams<T> wp) {
     constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, true>, ITEMS = kSplitKernel<T, false>, ROOT2 = false;
     constexpr bool RAYS = kSplitKernel<T, false>;
     constexpr int MODE = kModeV2;
-    const KParams<T>& p = wp.s.k;
 #include "rt_trace_body.hpp"
 }
 
@@ -135,7 +133,6 @@ __global__ __launch_bounds__(256, W) void trace_paths_items(IParams<T> ip) {
     constexpr bool SPLIT = kSplitKernel<T, true>, WIN = kSplitKernel<T, false>, ITEMS = kSplitKernel<T, true>, ROOT2 = false;
     constexpr bool RAYS = kSplitKernel<T, false>;
     constexpr int MODE = kModeV2;
-    const KParams<T>& p = ip.w.s.k;
 #include "rt_trace_body.hpp"
 }
 

@@ -2,7 +2,7 @@
 // trace_paths and of trace_paths_split (rt_trace.hpp; not a header on its own).  In scope: T, W, ROOT2, MODE,
 // CAMQ, MEGA, SPLIT, WIN (SPLIT only: the items tile a sample window, WParams<T>), ITEMS (SPLIT only: the items
 // are read from a table, IParams<T>), RAYS (trace_paths_rays, rt_rays.hpp: the primary rays are the caller's,
-// RParams<T>) and the kernel arguments p (KParams<T>).
+// RParams<T>).  The kernel arguments (KParams<T>) are read through cold_args<T>().
     constexpr bool SC = MODE == kModeScalar;
     static_assert(!SPLIT || (MODE == kModeV2 && !ROOT2), "the sample-parallel kernels cover the live path only");
     static_assert(!ITEMS || (SPLIT && !WIN), "an item table replaces the window's decode");
@@ -476,7 +476,7 @@
         const uint32_t depth = cold_args<T>()->depth;
         const bool act = live && k < depth;
         hit_i = -1;
-        if (act) hit_i = nearest_hit<T, ROOT2, SC, false, MEGA>(p, o, d, hit_t);
+        if (act) hit_i = nearest_hit<T, ROOT2, SC, MEGA>(o, d, hit_t);
         const unsigned long long bact = __ballot(act);
         if (lane == 0 && bact) { wcount[wave][0] += (uint32_t)__popcll(bact); wcount[wave][1] += 64u; }
         // ---- terminations: record e (and the colour of a sky hit) ----

@@ -141,7 +141,7 @@ __global__ void __launch_bounds__(kBlock) k_probe_general(KParams<T> p, const T*
     if (active[i]) {
         const V3<T> ro = ld3(o, n, i), rd = ld3(d, n, i);
         T th;
-        const int h = nearest_hit<T, ROOT2, SC, false, MEGA>(p, ro, rd, th);
+        const int h = nearest_hit<T, ROOT2, SC, MEGA>(ro, rd, th);
         idx[i] = h;
         t[i] = th;
     }

@@ -231,7 +231,7 @@ def _probe(name, flat, mode, filter_off, first, d, active):
 
 
 def probe_general(flat, mode, o, d, active, filter_off=False):
-    """nearest_hit<T, ROOT2, SCALAR, false, MEGA> for the active lanes of n rays (o, d: [3, n], n a multiple of 256;
+    """nearest_hit<T, ROOT2, SCALAR, MEGA> for the active lanes of n rays (o, d: [3, n], n a multiple of 256;
     lane i of the launch holds ray i).  Returns (idx [n] int32, t [n]); -1 / +inf: no hit; inactive lanes hold
     IDX_UNTOUCHED / T_UNTOUCHED."""
     o = np.ascontiguousarray(o)

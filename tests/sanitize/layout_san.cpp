@@ -22,11 +22,8 @@ static void check_tables(const SceneImage& im, const SceneTables<T>& t, size_t n
     const size_t ns = 4 * (size_t)n.n_xg + 16 * ncl, nsg = ((size_t)n.n_top + 3) / 4, nmg = (nsg + 3) / 4;
     const size_t one = n.n_spheres ? n.n_spheres : 1;
     constexpr size_t NE = 64 / sizeof(T), G = kGroup<T>;
-    CHECK(t.k.n_groups == (n.n_spheres + G - 1) / G);
-    CHECK(t.sph.size() == NE * ((size_t)t.k.n_groups + 1));
     CHECK(t.cen.size() == 4 * one);
     CHECK(t.mats.size() == one);
-    CHECK(t.fsph.size() == 16 * ((size_t)n.n_fgroups + 1));
     CHECK(t.rsph.size() == NE * (ns / G + 1));
     CHECK(t.top.size() == kBoxFloats * ((size_t)n.n_top + 1));   // n_top + 1 groups
     CHECK(t.sup.size() == kBoxFloats * (nsg + 1));
@@ -50,8 +47,6 @@ static void check_tables(const SceneImage& im, const SceneTables<T>& t, size_t n
         CHECK(t.lbx[2].size() == kLBoxFloats * (nmg + 1));
         CHECK(t.lbx[3].size() == kLBoxFloats * ((nmg + 3) / 4 + 1));
     }
-    CHECK(t.cam_bytes.cam == t.sph.size() * sizeof(T));
-    CHECK(t.cam_bytes.camf == t.fsph.size() * sizeof(float));
     CHECK(t.cam_bytes.camx == 4 * (size_t)n.n_cslots * sizeof(T));
     CHECK(t.cam_bytes.cull == 4 * (size_t)n.n_cslots * sizeof(float));
     CHECK(t.cam_bytes.cullc == t.clus.size() * sizeof(float));
@@ -65,8 +60,6 @@ static void check_scene(const rt_scene& s) {
     for (const auto& m : L.members) CHECK(m.size() <= kClusterMax);   // no cluster has more than 16 members
     CHECK(ncl % 4 == 0 && n.n_top == ncl / 4);
     CHECK(n.n_spheres == s.n_spheres);
-    CHECK(n.n_fgroups == (s.n_spheres + 3) / 4);
-    CHECK(n.n_cull == (s.n_spheres + 63) / 64 * 64 + 64);
     CHECK(n.n_cslots == 4 * n.n_xg + 16 * ncl + 64);
     CHECK(n.n_clp % 64 == 0 && n.n_clp >= ncl);
     CHECK(n.n_supc % 64 == 0 && (n.n_supc != 0) == (ncl > 128) && (n.n_supc == 0 || n.n_supc >= ncl / 4));

@@ -2,7 +2,7 @@
 every path of the kernel that tests/test_gpu_guides.py leaves unreached.
 
 The guide kernel runs the render kernels' culls with template arguments no render uses (camera_listed<T, false,
-false> with a one-slot mask, camera_sweep<T, false, false, MEGA>, nearest_hit<T, false, false, false, MEGA> at
+false> with a one-slot mask, camera_sweep<T, false, false, MEGA>, nearest_hit<T, false, false, MEGA> at
 bounce 0 only) and its own copy of PackedHitRecords::finalize, and its outputs show what an image hides: the
 hit index (albedo is the material of `hi`), the normal's sign, and t itself as float32.
 
@@ -183,7 +183,7 @@ def test_layout_families(renderer, prec, name):
 @pytest.mark.parametrize("prec", PRECS)
 def test_defocus_mega(renderer, prec):
     """guide_pixels<T, false, true>: config E's 10 000 spheres through a lens, every primary ray through
-    nearest_hit<T, false, false, false, true> (the super level of the general sweep) at bounce 0."""
+    nearest_hit<T, false, false, true> (the super level of the general sweep) at bounce 0."""
     _, idx = samples(("defocus_mega",), prec)
     assert len(np.unique(idx)) > 8
     _, st = run(renderer, ("defocus_mega",), prec, camq=False, mega=True)
