@@ -140,6 +140,9 @@ typedef struct rt_stats {
 /* Set: the caller-ray kernel ran, trace_paths_rays<T, W, ROOT2, MEGA> (rt_render_rays_async; rays_validate<T> runs
  * ahead of it); F64, WAVES, ROOT2 and MEGA mean what they mean above, CAMQ, MODE, SPLIT, ITEMS, GUIDES and QUERY are 0. */
 #define RT_KERNEL_RAYS(id) (((id) >> 13) & 1u)
+/* Set: the occlusion kernel ran, occlusion_rays<T, ROOT2, MEGA> (rt_query_occluded_async); F64, WAVES, ROOT2 and MEGA
+ * mean what they mean above, CAMQ, MODE, SPLIT, ITEMS, GUIDES, QUERY and RAYS are 0. */
+#define RT_KERNEL_OCCLUSION(id) (((id) >> 14) & 1u)
 
 /* ---- flags ---- */
 #define RT_FLAG_F32 0x1u     /* compute in fp32 (default: fp64, the reference's arithmetic) */
@@ -302,12 +305,51 @@ int rt_render_guides_async(rt_context* ctx, const rt_camera* camera, uint32_t sp
  * rt_context_collect after it: pixels = n_rays, samples = ray_segments = the valid rays, bounce_iters = 0, lane_slots
  * 64 per batch of 64 consecutive rays with a valid ray in it, RT_KERNEL_QUERY(kernel_id) is set; the executed-work
  * counters hold what the reused sweeps count.
- * Out of scope: sorting or binning incoherent rays, a per-ray t_max or an any-hit exit, the scalar mode, radiance. */
+ * Out of scope: sorting or binning incoherent rays, the scalar mode, radiance (a per-ray t_max and the any-hit exit:
+ * rt_query_occluded_async below). */
 #define RT_QUERY_MISS (-1)
 #define RT_QUERY_INVALID (-2)
 int rt_query_hits_async(rt_context* ctx, uint64_t n_rays, const void* d_origins, const double* origin,
                         const void* d_directions, uint32_t flags, void* d_t, void* d_index, void* d_normal,
                         void* d_point, void* d_front, void* stream);
+/* ---- occlusion queries: is anything in the way before t_max ----
+ * Shadow rays towards a light, ambient occlusion, visibility between two points, line of sight: n_rays rays, each with
+ * a bound t_max of its own, one byte per ray.  T is float under RT_FLAG_F32 and double otherwise.  The sweep stops
+ * working for a ray at its first accepted hit and never enters a box that lies wholly past the ray's t_max.
+ * Definition, per ray (o, d, t_max), in T:
+ *   occluded  some sphere's accepted root r satisfies r < t_max, strictly.  The accepted root is exactly
+ *             rt_query_hits_async's hit rule: Sphere::hit_packed's near root when it lies in [0.001, inf); quirk Q1
+ *             applies unless RT_FLAG_ROOT2, which accepts the far root when the near one is not valid.  Equivalently:
+ *             rt_query_hits_async's closest hit of (o, d) exists and its t < t_max.  Strict, so a shadow ray whose
+ *             t_max is the t of a known hit does not report that hit.  Directions are NOT normalised, so d = light - p
+ *             with t_max = 1 asks about the open segment up to the light.
+ *   valid     a ray is valid when it meets rt_query_hits_async's precondition (finite components, |d|^2 in T within
+ *             [1e-6, 1e6], the bounds themselves valid) and its t_max is not NaN.  t_max may be +inf (unbounded),
+ *             negative, zero or -inf.  A valid ray with t_max <= T(0.001) is never occluded and is not traced.
+ * Output: d_occluded, device uint8 [n_rays]: 0 (RT_OCCLUDED_NO) not occluded, 1 (RT_OCCLUDED_YES) occluded, 255
+ * (RT_OCCLUDED_INVALID) an invalid ray, not traced.  No ray's value depends on any other ray.
+ * Rays: d_directions and the two origin forms are rt_query_hits_async's (exactly one form; a shared origin is rounded
+ * as (T)origin[i] and broadcast).  Both forms run the general sweep, as rt_render_rays_async does (no camera tables),
+ * and give identical bytes.
+ * t_max: d_t_max is device [n_rays] of T, or NULL; when NULL every ray uses (T)t_max, when given the host t_max is
+ * not read.
+ * flags: RT_FLAG_F32 and RT_FLAG_ROOT2.  Any RT_FLAG_MODE_* is RT_ERR_UNSUPPORTED; unknown bits are RT_ERR_INVALID.
+ * n_rays == 0: RT_OK, nothing is enqueued.  n_rays > 0x7FFFFFFF: RT_ERR_UNSUPPORTED.  RT_ERR_INVALID, checked before
+ * any HIP call: ctx, d_directions or d_occluded NULL, both or neither origin form, d_t_max NULL and the host t_max NaN,
+ * no scene set.
+ * Asynchronous on `stream` under rt_render_async's cross-stream rule.  Allowed while a progressive session is open;
+ * touches neither its records nor its counts.
+ * rt_context_collect after it: pixels = n_rays, samples = ray_segments = the valid rays, bounce_iters = 0, lane_slots
+ * 64 per batch of 64 consecutive rays of which at least one entered the sweep (valid, t_max > 0.001),
+ * RT_KERNEL_OCCLUSION(kernel_id) is set; the executed-work counters hold what the sweep counted before it stopped.
+ * Out of scope: a shared-origin path over the camera tables, sorting or binning incoherent rays, which sphere
+ * occludes, a t_min other than 0.001, the scalar and vectorized* modes. */
+#define RT_OCCLUDED_NO 0
+#define RT_OCCLUDED_YES 1
+#define RT_OCCLUDED_INVALID 255
+int rt_query_occluded_async(rt_context* ctx, uint64_t n_rays, const void* d_origins, const double* origin,
+                            const void* d_directions, const void* d_t_max, double t_max, uint32_t flags,
+                            void* d_occluded, void* stream);
 /* ---- rendering caller-supplied primary rays: any camera model, full paths ----
  * rt_render_async with the primary rays taken from the caller's arrays instead of Camera::get_ray: an orthographic
  * view, a fisheye, a 360 degree panorama (rt_camera_rays below makes their rays) or the rays of the caller's own

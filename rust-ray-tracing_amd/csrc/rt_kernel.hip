@@ -31,7 +31,7 @@
 // layout and device code share; no HIP), rt_common.hpp (kernel arguments, scalar-load pipelines),
 // rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (the record view, replay + reduction),
 // rt_trace.hpp + rt_trace_body.hpp (the persistent kernel), rt_guides.hpp (guide buffers: first hits only),
-// rt_query.hpp (ray queries: the closest hit of the caller's rays), rt_rays.hpp (full paths for the caller's
+// rt_query.hpp (ray queries: the closest hit of the caller's rays, and occlusion before a t_max), rt_rays.hpp (full paths for the caller's
 // primary rays); rt_projection.hpp (host only: the rays of camera models the reference lacks);
 // host only, without HIP: rt_layout.hpp (the scene image: every device table of a scene, build_scene_image),
 // rt_split_plan.hpp (the sample-parallel plan), rt_progressive_plan.hpp (a progressive session's record buffer,
@@ -41,7 +41,7 @@
 // launch_cam_table; it knows no context, and the test-only device library builds its arguments with it),
 // rt_launch.hpp (what a context's launches share, kernel selection and kernel_id, the launch steps frame_params,
 // ensure_cam_tables, frame_setup, plan_grid, and the launchers launch_plain, launch_split, launch_window,
-// launch_guides, launch_query, launch_rays), rt_session.hpp (a progressive session: its state, launch_items and launch_classes
+// launch_guides, launch_query, launch_occlusion, launch_rays), rt_session.hpp (a progressive session: its state, launch_items and launch_classes
 // for per-pixel counts, extend_uniform, run_map, snapshot_run and the steps of refine_step).  This file holds the
 // C ABI: rt_context, the entry points (their argument checks, then one call) and the small device helpers.
 #include "rt_session.hpp"
@@ -314,6 +314,29 @@ extern "C" int rt_query_hits_async(rt_context* c, uint64_t n_rays, const void* d
     int rc = begin_launch(c, st);
     if (rc != RT_OK) return rc;
     rc = with_precision((flags & RT_FLAG_F32) != 0, [&](auto t) { return launch_query<decltype(t)>(c, a, st); });
+    if (rc != RT_OK) return rc;
+    return end_launch(c, st, n_rays, 0u);   // samples: the valid rays, counted on the device (kQuerySlot)
+}
+
+extern "C" int rt_query_occluded_async(rt_context* c, uint64_t n_rays, const void* d_origins, const double* origin,
+                                       const void* d_directions, const void* d_t_max, double t_max, uint32_t flags,
+                                       void* d_occluded, void* stream) {
+    const std::string who = "rt_query_occluded_async";
+    if (!c || !d_directions || !d_occluded) return fail(RT_ERR_INVALID, who + ": NULL argument (ctx, d_directions or d_occluded)");
+    if ((d_origins != nullptr) == (origin != nullptr))
+        return fail(RT_ERR_INVALID, who + ": exactly one of d_origins (per ray) and origin (shared) must be given");
+    if (!d_t_max && t_max != t_max) return fail(RT_ERR_INVALID, who + ": d_t_max is NULL and t_max is NaN");
+    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
+    if (flags & ~(RT_FLAG_F32 | RT_FLAG_ROOT2))
+        return fail(RT_ERR_UNSUPPORTED, who + ": the live path's hit rule only (RT_FLAG_F32, RT_FLAG_ROOT2; no RT_FLAG_MODE_*)");
+    if (n_rays > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many rays in one call");
+    if (!c->has_scene) return fail(RT_ERR_INVALID, who + ": no scene set (rt_context_set_scene first)");
+    if (n_rays == 0) return RT_OK;
+    const OcclusionArgs a{n_rays, d_origins, origin, d_directions, d_t_max, t_max, flags, d_occluded};
+    hipStream_t st = (hipStream_t)stream;
+    int rc = begin_launch(c, st);
+    if (rc != RT_OK) return rc;
+    rc = with_precision((flags & RT_FLAG_F32) != 0, [&](auto t) { return launch_occlusion<decltype(t)>(c, a, st); });
     if (rc != RT_OK) return rc;
     return end_launch(c, st, n_rays, 0u);   // samples: the valid rays, counted on the device (kQuerySlot)
 }

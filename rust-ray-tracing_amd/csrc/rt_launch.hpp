@@ -1,7 +1,7 @@
 // rt_launch.hpp — the launches of the C ABI, host only: what the launches of a context share (LaunchContext),
 // the kernel selection and rt_stats.kernel_id, the steps of a launch (context_params, frame_params,
 // ensure_cam_tables, frame_setup, plan_grid) and the launchers (launch_plain, launch_split, launch_window,
-// launch_guides, launch_query, launch_rays), between begin_launch and end_launch.
+// launch_guides, launch_query, launch_occlusion, launch_rays), between begin_launch and end_launch.
 #pragma once
 #include "rt_trace.hpp"
 #include "rt_guides.hpp"
@@ -47,6 +47,7 @@ constexpr uint32_t kKernelItemsBit = 1u << 10;    // with kKernelSplitBit: a ses
 constexpr uint32_t kKernelGuidesBit = 1u << 11;   // guide_pixels
 constexpr uint32_t kKernelQueryBit = 1u << 12;    // query_rays (its SHARED takes the camera-batch bit)
 constexpr uint32_t kKernelRaysBit = 1u << 13;     // trace_paths_rays
+constexpr uint32_t kKernelOcclusionBit = 1u << 14;   // occlusion_rays
 template <typename T>
 constexpr uint32_t kernel_id(int W, bool root2, int mode, bool camq, bool mega, uint32_t family) {
     return 0x8000u | (sizeof(T) == 8 ? 1u : 0u) | ((uint32_t)W << 1) | (root2 ? kKernelRoot2Bit : 0u) |
@@ -131,6 +132,11 @@ static void (*pick_guides(bool camq, bool mega))(GParams<T>) {
 template <typename T>
 static void (*pick_query(bool root2, bool shared, bool mega))(QParams<T>) {
     return with_bools([](auto r2, auto sh, auto mg) { return query_rays<T, r2.value, sh.value, mg.value>; }, root2, shared, mega);
+}
+// The occlusion kernel (rt_query_occluded_async): occlusion_rays<T, ROOT2, MEGA>.
+template <typename T>
+static void (*pick_occlusion(bool root2, bool mega))(OParams<T>) {
+    return with_bools([](auto r2, auto mg) { return occlusion_rays<T, r2.value, mg.value>; }, root2, mega);
 }
 // The caller-ray kernel (rt_render_rays_async): trace_paths_rays<T, W, ROOT2, MEGA> at the precision's default W.
 template <typename T>
@@ -410,6 +416,48 @@ static int launch_query(LaunchContext* c, const QueryArgs& a, hipStream_t st) {
     qp.point = (T*)a.point;
     qp.front = (uint8_t*)a.front;
     hipLaunchKernelGGL(qfn, dim3((uint32_t)nblocks), dim3(256), 0, st, qp);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// What rt_query_occluded_async asks for: a query's rays, a bound per ray (d_t_max) or one for all (t_max), one byte out.
+struct OcclusionArgs {
+    uint64_t n_rays;
+    const void* origins;
+    const double* origin;
+    const void* directions;
+    const void* d_t_max;
+    double t_max;
+    uint32_t flags;
+    void* occluded;
+};
+
+// occlusion_rays: launch_query's grid.  A shared origin is rounded as a camera centre is and broadcast by the kernel;
+// both origin forms run the general sweep, so no camera tables are built or read.
+template <typename T>
+static int launch_occlusion(LaunchContext* c, const OcclusionArgs& a, hipStream_t st) {
+    KParams<T> p;
+    context_params(c, filter_off_env(), p);
+    p.flags = a.flags;
+    p.n_items = (uint32_t)a.n_rays;
+    if (a.origin) for (int i = 0; i < 3; ++i) p.center[i] = (T)a.origin[i];
+    const bool root2 = (a.flags & RT_FLAG_ROOT2) != 0u, mega = p.n_mg > 0;
+    void (*const ofn)(OParams<T>) = pick_occlusion<T>(root2, mega);
+    constexpr int W = kWavesQuery<T>;
+    const uint32_t id = kernel_id<T>(W, root2, kModeV2, false, mega, kKernelOcclusionBit);
+    const uint32_t n_batches = (uint32_t)((a.n_rays + 63u) / 64u);   // a wave's work item
+    uint64_t nblocks = 0;
+    const int rc = plan_grid(c, (const void*)ofn, W, id, n_batches, 1u, nblocks, p.blk_g);
+    if (rc != RT_OK) return rc;
+    OParams<T> op;
+    memset(&op, 0, sizeof(op));
+    op.k = p;
+    op.origins = (const T*)a.origins;
+    op.directions = (const T*)a.directions;
+    op.t_max = (const T*)a.d_t_max;
+    op.t_max_all = (T)a.t_max;
+    op.occluded = (uint8_t*)a.occluded;
+    hipLaunchKernelGGL(ofn, dim3((uint32_t)nblocks), dim3(256), 0, st, op);
     HIPCHK(hipGetLastError());
     return RT_OK;
 }

@@ -3,7 +3,8 @@
 // One kernel, query_rays<T, ROOT2, SHARED, MEGA>: the live path's closest hit through the sweeps the trace kernels
 // run (nearest_hit for rays with origins of their own, camera_sweep over the camera tables of a shared origin),
 // then PackedHitRecords::finalize (objects.rs:157-162) as guide_pixels has it, and plain vector stores.  It stops
-// there: no scatter, no records, no reduction.
+// there: no scatter, no records, no reduction.  occlusion_rays<T, ROOT2, MEGA> (rt_query_occluded_async, at the end of
+// this file) answers "is anything in the way before t_max" under the same mapping and precondition.
 //
 // Mapping: the lane is the ray, a batch is 64 consecutive rays, and the waves stride over the batches.  A ray
 // outside the precondition (include/rt_mi355x.h: a non-finite component, or |d|^2 outside [1e-6, 1e6], the range
@@ -113,6 +114,82 @@ __global__ __launch_bounds__(256, kWavesQuery<T>) void query_rays(QParams<T> qp)
             }
             if (qp.front) qp.front[ray] = front ? 1u : 0u;
         }
+    }
+    if (lane == 0) {
+        const auto& q = *cold_args<T>();
+        unsigned long long* cc = &q.segs[(gw & (kSegShards - 1)) * kSegStride];
+        if (n_seg) {
+            atomicAdd(cc + 0, n_seg);
+            atomicAdd(cc + kQuerySlot, n_seg);
+        }
+        if (n_slots) atomicAdd(cc + 1, n_slots);
+        for (uint32_t i = 0; i < kNWork; ++i)
+            if (g_work[wave][i]) atomicAdd(cc + kWorkSlot + i, g_work[wave][i]);
+#ifdef RT_KSTATS
+        for (int i = 0; i < kNKstat; ++i) atomicAdd(cc + kstat_slot(i), g_kst[wave][i]);
+#endif
+    }
+}
+
+// ---- occlusion queries (rt_query_occluded_async): is anything in the way before t_max ----
+// One kernel, occlusion_rays<T, ROOT2, MEGA>, under query_rays' mapping: one byte per ray, kOccluded* below.  A ray
+// is valid under the query's precondition when its t_max is not NaN; a valid ray with t_max <= 0.001 has no
+// accepted root below its bound and does not enter the sweep.  The others go through nearest_hit's any-hit variant
+// (rt_sweep.hpp: the bound culls boxes from the first group, a lane is done at its first accepted hit, the wave
+// leaves when every lane is).  Origins of their own or one shared origin (k.center), both through the general sweep.
+// Arguments: KParams first, as QParams has it; t_max: per ray, or NULL for t_max_all.
+template <typename T> struct OParams {
+    KParams<T> k;
+    const T* origins;      // [n][3]; NULL: the shared origin k.center
+    const T* directions;   // [n][3]
+    const T* t_max;        // [n]; NULL: t_max_all
+    T t_max_all;
+    uint8_t* occluded;     // [n]
+};
+constexpr uint8_t kOccludedNo = RT_OCCLUDED_NO, kOccludedYes = RT_OCCLUDED_YES, kOccludedInvalid = RT_OCCLUDED_INVALID;
+
+template <typename T, bool ROOT2, bool MEGA>
+__global__ __launch_bounds__(256, kWavesQuery<T>) void occlusion_rays(OParams<T> op) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (lane < kNWork) g_work[wave][lane] = 0ull;
+#ifdef RT_KSTATS
+    if (lane < kNKstat) g_kst[wave][lane] = 0;
+#endif
+    const uint32_t gw = blockIdx.x * 4u + wave, nw = gridDim.x * 4u;
+    const uint32_t n = cold_args<T>()->n_items;   // <= 0x7FFFFFFF rays
+    const uint32_t n_batches = (n + 63u) / 64u;   // <= 2^25: batch + nw does not wrap
+    unsigned long long n_seg = 0, n_slots = 0;
+    for (uint32_t batch = gw; batch < n_batches; batch += nw) {
+        const uint32_t ray = batch * 64u + lane;   // <= 0x7FFFFFFF + 63
+        const bool in = ray < n;
+        V3<T> o = mk(T(0), T(0), T(0)), d = o;
+        T tm = T(0);
+        if (in) {
+            const T* dp = op.directions + (size_t)3 * ray;
+            d = mk(dp[0], dp[1], dp[2]);
+            if (op.origins == nullptr) {   // wave-uniform
+                const auto& q = *cold_args<T>();
+                o = mk(q.center[0], q.center[1], q.center[2]);
+            } else {
+                const T* pp = op.origins + (size_t)3 * ray;
+                o = mk(pp[0], pp[1], pp[2]);
+            }
+            tm = op.t_max != nullptr ? op.t_max[ray] : op.t_max_all;
+        }
+        const T a = pk_len2(d);
+        const bool v = in && query_finite(o) && query_finite(d) && a >= kQueryLen2Min<T> && a <= kQueryLen2Max<T> && tm == tm;
+        const bool go = v && tm > T(0.001);   // a root is accepted from 0.001 on: nothing lies below such a bound
+        bool occ = false;
+        if (__ballot(go) != 0ull) {   // wave-uniform
+            if (go) {
+                T t = tm;
+                occ = nearest_hit<T, ROOT2, false, MEGA, true>(o, d, t) >= 0;
+            }
+            n_slots += 64u;
+        }
+        n_seg += (unsigned long long)__builtin_popcountll(__ballot(v));
+        if (in) op.occluded[ray] = v ? (occ ? kOccludedYes : kOccludedNo) : kOccludedInvalid;
     }
     if (lane == 0) {
         const auto& q = *cold_args<T>();

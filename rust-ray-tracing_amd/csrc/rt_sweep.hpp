@@ -174,16 +174,37 @@ __device__ __forceinline__ void hit_update(T hb, T disc, uint32_t i, T a, T inv_
     }
 }
 
+// The any-hit sweep's seed (nearest_hit, ANY): the bound t_max with an index above every sphere's.  A lane is open
+// while the seed's index is still there; the wave's sweep is closed when no active lane is open.
+__device__ __forceinline__ void any_seed(HitBest<float>& bh, float t_max) { bh.k = hit_key(t_max, 0xFFFFFFFFu); }
+__device__ __forceinline__ void any_seed(HitBest<double>& bh, double t_max) { bh.set(t_max, 0x7FFFFFFFu); }
+__device__ __forceinline__ bool any_open(const HitBest<float>& bh) { return (uint32_t)bh.k == 0u; }
+__device__ __forceinline__ bool any_open(const HitBest<double>& bh) { return bh.i == 0x7FFFFFFF; }
+template <typename T> __device__ __forceinline__ bool any_closed(const HitBest<T>& bh) { return __ballot(any_open(bh)) == 0ull; }
+
 // The object loop of trace_vectorized2 for one enabled ray (ray_tracing.rs:399-403): returns the
 // index of the nearest valid hit (-1: the sky, :421-424) and its t.
 // SCALAR selects Sphere::hit + Scene::hit (objects.rs:216-247, ray_tracing.rs:231-235): no FMA,
 // both roots, root = (-hb -/+ sd) / a, the first minimum wins ties.  Otherwise hit_packed +
 // PackedHitRecords::update (objects.rs:249-290, 140-155).
-template <typename T, bool root2, bool SCALAR = false, bool MEGA = false>
+// ANY (occlusion_rays, rt_query.hpp): is some accepted root below t_out, strictly?  t_out comes in as the ray's
+// bound t_max (> 0.001, not NaN) and the result is >= 0 iff one is.  The best hit starts at (t_max, an index above
+// every sphere's) instead of (+inf, -1), so hit_update's one compare is exactly r < t_max (fp32: the seed key's low
+// half is 0 and a sphere's is >= 1; fp64: the tie rule i > INT_MAX never holds), and btf() hands the box tests
+// t_max from the first group on: the argument above box_pair needs tn <= t* for a reportable root, not that bt is
+// one.  A lane that has accepted a hit is done: the best hit only ever replaces the seed by a root below t_max, so
+// "the seed's index is gone" is the lane's verdict whatever it tests later.  A done lane gives the box tests a
+// negative bound (max(tn, 0) <= min(tf, bt) fails for every box: one that holds the origin, a degenerate lane's NaN
+// times too, since v_min_f32 returns the bound), drops its flush candidates, and when no lane of the wave is open
+// the sweep returns: after the always-exact groups (the top of the first chunk), and before every walked super
+// and mega (a ballot and a scalar branch each; a break lands on the enclosing loop's own test, so no state is kept).
+template <typename T, bool root2, bool SCALAR = false, bool MEGA = false, bool ANY = false>
 __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_out) {
+    static_assert(!(ANY && SCALAR), "the any-hit sweep is the live path's");
     const T a = SCALAR ? len2(d) : pk_len2(d);       // objects.rs:219 / :253
     const T inv_a = SCALAR ? T(0) : T(1.0) / a;      // objects.rs:254 (loop-invariant)
     HitBest<T> bh;                   // PackedHitRecords::default, objects.rs:128
+    if constexpr (ANY) any_seed(bh, t_out);
     // Sphere::hit_packed (objects.rs:249-290) + PackedHitRecords::update (objects.rs:140-155)
     // for a candidate whose discriminant is non-negative.  Exact pre-filter: with hb >= 0,
     // root1 = (-hb - sd)*inv_a <= 0 can never be valid, so only Q1-off (root2) mode needs it.
@@ -282,8 +303,15 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
     // 1 + m / (2 r2min) + 8 u pm / sqrt(r2min) as fma(pm^2 + r2max, 48 u 0.5 / r2min, fma(pm, 8 u /
     // sqrt(r2min), 1)): the margin factor folded into the host constant (box_cull_fuzz models this).
     // The best hit so far as a box-time bound (box_pair): fp64 rounds it up to a float.
+    // ANY: t_max (t_out still holds it) while the lane is open (b > 0: only rays with t_max > 0.001 enter), negative
+    // once it is done.
     auto btf = [&]() -> float {
-        if constexpr (sizeof(T) == 4) return bh.bt();
+        if constexpr (ANY) {
+            if (!any_open(bh)) return -1.0f;
+            if constexpr (sizeof(T) == 4) return t_out;
+            else return (float)t_out * (1.0f + 0x1.0p-22f);
+        }
+        else if constexpr (sizeof(T) == 4) return bh.bt();
         else return (float)bh.bt() * (1.0f + 0x1.0p-22f);   // RN(RN(b) (1 + 2^-22)) > b (b > 0)
     };
     const f2 nixy = {-ix, -iy}, aixy = {fabsf(ix), fabsf(iy)};
@@ -396,6 +424,7 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
         if constexpr (sizeof(T) == 4) {
             const cptr<char> fl = (cptr<char>)__builtin_assume_aligned(qa.rflat, 16) + 64u * nxg;
             const cptr<char> ri = (cptr<char>)__builtin_assume_aligned(qa.ridx, 16) + 16u * nxg;
+            if constexpr (ANY) cand = any_open(bh) ? cand : 0u;   // a done lane's candidates are dropped
             while (__ballot(cand != 0u) != 0ull) {
                 KSTAT(0);
                 ++n_exact;
@@ -420,6 +449,7 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
                     // dependent round trip per step)
                     asm volatile("" : "+v"(si));
                     if (cand_f(hb, disc)) hit(hb, disc, si);
+                    if constexpr (ANY) cand = any_open(bh) ? cand : 0u;
                 }
             }
         }
@@ -575,6 +605,7 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
             uint32_t smask = lmask(load_lbox(ls, nd));
             if (4u * nd + 4u > ntop) smask &= (1u << (ntop - 4u * nd)) - 1u;   // padding supers
             while (smask != 0u) {
+                if constexpr (ANY) { if (any_closed(bh)) break; }
                 const uint32_t sup = 4u * nd + (uint32_t)__builtin_ctz(smask);
                 smask &= smask - 1u;
                 walk_super(sup);
@@ -587,6 +618,7 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
         const uint32_t span = ntg <= 16u ? 16u : 8u;
         constexpr uint32_t kTest = 1;   // the tiers below kTest are walked before the top-level tests
         for (uint32_t t0 = 0; t0 < ntg; t0 += span) {
+            if constexpr (ANY) { if (any_closed(bh)) break; }
             const uint32_t nt = min(span, ntg - t0);
             // padding megas (empty boxes) past the last
             const uint64_t valid = 4u * (t0 + nt) > nsg ? (1ull << (nsg - 4u * t0)) - 1ull : ~0ull;
@@ -615,6 +647,7 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
             uint64_t tm = 0;
 #pragma unroll 1
             for (uint32_t k = 0; k < 3u; ++k) {
+                if constexpr (ANY) { if (any_closed(bh)) break; }
                 if (k == kTest) {
                     const uint32_t ngg = span == 16u ? qa.n_gg : 0u;
                     if (ngg != 0u) {
@@ -645,6 +678,7 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
                 uint64_t w = k == 0u ? (kTest == 0u ? tm & T0 : T0)
                                      : (k == 1u ? (kTest <= 1u ? tm & T1 : T1) & ~T0 : tm & ~T1);
                 while (w != 0ull) {
+                    if constexpr (ANY) { if (any_closed(bh)) break; }
                     const uint32_t nd = 4u * t0 + (uint32_t)__builtin_ctzll(w);
                     w &= w - 1ull;
                     walk_mega(nd);
@@ -653,6 +687,7 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
         }
     } else {
         for (uint32_t t0 = 0; t0 < nsg; t0 += 8u) {
+            if constexpr (ANY) { if (any_closed(bh)) break; }
             uint32_t tmask = 0;
             n_box += min(8u, nsg - t0);
             box_loop(fs + kBoxFloats * t0, min(8u, nsg - t0), [&](const BoxGroup& cur, uint32_t t) {
@@ -665,6 +700,7 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
                 // padding supers past the last one are empty boxes; a degenerate lane (all box
                 // times NaN) passes them, and nothing lies behind them
                 if (nd >= ntop) break;
+                if constexpr (ANY) { if (any_closed(bh)) break; }
                 walk_super(nd);
             }
         }
@@ -681,7 +717,8 @@ __device__ __forceinline__ int nearest_hit(const V3<T>& o, const V3<T>& d, T& t_
     work_add(kWFilt, n_filt);
     work_add(kWExact, n_exact);
     t_out = bh.bt();
-    return bh.bi();
+    if constexpr (ANY) return any_open(bh) ? -1 : 0;
+    else return bh.bi();
 }
 
 }  // namespace rt

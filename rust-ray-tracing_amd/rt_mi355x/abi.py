@@ -111,8 +111,16 @@ def RT_KERNEL_RAYS(kernel_id):
     return (kernel_id >> 13) & 1
 
 
+def RT_KERNEL_OCCLUSION(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_OCCLUSION: the occlusion kernel ran (rt_query_occluded_async)."""
+    return (kernel_id >> 14) & 1
+
+
 RT_QUERY_MISS = -1      # include/rt_mi355x.h: rt_query_hits_async's index of a ray that hits nothing
 RT_QUERY_INVALID = -2   # ... and of a ray outside the precondition (not traced)
+RT_OCCLUDED_NO = 0          # include/rt_mi355x.h: rt_query_occluded_async's byte of a ray with nothing before its t_max,
+RT_OCCLUDED_YES = 1         # ... of a ray with an accepted root below its t_max,
+RT_OCCLUDED_INVALID = 255   # ... and of a ray outside the precondition or with a NaN t_max (not traced)
 
 
 def kernel_info(kernel_id):
@@ -123,7 +131,7 @@ def kernel_info(kernel_id):
             "mode": (kernel_id >> 5) & 3, "camq": bool((kernel_id >> 7) & 1), "mega": bool((kernel_id >> 8) & 1),
             "split": bool(RT_KERNEL_SPLIT(kernel_id)), "items": bool(RT_KERNEL_ITEMS(kernel_id)),
             "guides": bool(RT_KERNEL_GUIDES(kernel_id)), "query": bool(RT_KERNEL_QUERY(kernel_id)),
-            "rays": bool(RT_KERNEL_RAYS(kernel_id))}
+            "rays": bool(RT_KERNEL_RAYS(kernel_id)), "occlusion": bool(RT_KERNEL_OCCLUSION(kernel_id))}
 
 
 def kernel_name(kernel_id):
@@ -132,6 +140,8 @@ def kernel_name(kernel_id):
     if k is None:
         return None
     b = lambda v: "true" if v else "false"
+    if k["occlusion"]:   # occlusion_rays<T,ROOT2,MEGA>
+        return f"occlusion_rays<{k['T']},{b(k['root2'])},{b(k['mega'])}>"
     if k["rays"]:   # trace_paths_rays<T,W,ROOT2,MEGA> (rays_validate<T> runs ahead of it)
         return f"trace_paths_rays<{k['T']},{k['W']},{b(k['root2'])},{b(k['mega'])}>"
     if k["query"]:   # query_rays<T,ROOT2,SHARED,MEGA> (SHARED in the CAMQ bit)
@@ -174,6 +184,7 @@ EXPORTED = [
     "rt_progressive_extend_map_async", "rt_progressive_snapshot_map_async", "rt_progressive_counts",
     "rt_progressive_error_async", "rt_progressive_map_plan", "rt_progressive_refine", "rt_progressive_refine_items",
     "rt_render_guides_async", "rt_query_hits_async", "rt_memcpy_h2d", "rt_render_rays_async", "rt_camera_rays",
+    "rt_query_occluded_async",
 ]
 
 _lib = None
@@ -236,6 +247,7 @@ def load_library(path=None):
     lib.rt_render_split_async.argtypes = [vp, P(RtCamera), u32, u32, u64, u32, P(RtTileRange), vp, vp, vp, u32]
     lib.rt_render_guides_async.argtypes = [vp, P(RtCamera), u32, u64, u32, P(RtTileRange), vp, vp, vp, vp, vp]
     lib.rt_query_hits_async.argtypes = [vp, u64, vp, P(f64), vp, u32, vp, vp, vp, vp, vp, vp]
+    lib.rt_query_occluded_async.argtypes = [vp, u64, vp, P(f64), vp, vp, f64, u32, vp, vp]
     lib.rt_render_rays_async.argtypes = [vp, u64, u32, u32, vp, P(f64), vp, u32, u64, u32, u32, vp, vp, vp]
     lib.rt_camera_rays.argtypes = [P(RtProjection), u32, u32, vp, vp]
     lib.rt_split_plan.argtypes = [u64, u32, u32, P(u32), P(u64)]

@@ -21,6 +21,7 @@ from . import abi
 from .checks import (ADAPTIVE_PLANS, GUIDE_CHANNELS, GUIDE_NAMES, QUERY_NAMES, QUERY_OUTPUTS, Guides,  # noqa: F401
                      _device_array, _query_shape, check_adaptive, check_guides, check_query, check_query_into,
                      check_render_rays, check_render_rays_into, check_schedule, check_stream, split_argument)
+from .occlusion_checks import check_occluded, check_occluded_into, check_scene_set  # noqa: F401
 
 
 class RenderStat:
@@ -411,6 +412,52 @@ class GpuRenderer(Renderer):
         if self._scene_flat is None:
             raise RuntimeError("query_into needs a scene: call set_scene first")
         abi.check(self.lib, self._launch_query(n, d_org, origin, d_dir, flags, ptrs, stream))
+        return n
+
+    def _launch_occluded(self, n, d_org, origin, d_dir, d_t_max, t_max, flags, d_occ, stream):
+        return self.lib.rt_query_occluded_async(self.ctx, n, d_org, _pointer(origin, abi.f64), d_dir, d_t_max, t_max,
+                                                flags, d_occ, stream)
+
+    def occluded(self, origins, directions, scene, t_max=np.inf, root2=False):
+        """rt_query_occluded_async with numpy arrays: is anything in the way of each ray before its t_max
+        (include/rt_mi355x.h has the definition).  directions: (n, 3), not normalised, so d = light - p with t_max = 1
+        asks about the open segment up to the light; origins: (n, 3), or (3,) for one shared origin; t_max: a number
+        (not NaN; the default +inf: unbounded) or an (n,) array, one bound per ray.  The arrays are converted to the
+        renderer's precision.  root2: quirk Q1 off, as in query().
+        Returns uint8 (n,): abi.RT_OCCLUDED_NO = 0, abi.RT_OCCLUDED_YES = 1 (an accepted root r < t_max, strictly),
+        abi.RT_OCCLUDED_INVALID = 255 (a ray outside query()'s precondition or with a NaN t_max: not traced).  The
+        call's RtStats are kept in self.query_stats."""
+        flags = self._query_flags(root2)
+        o, d, shared, t = check_occluded(flags, origins, directions, t_max)   # before any GPU call
+        n = d.shape[0]
+        out = np.empty(n, dtype=np.uint8)
+        self._use_scene(_flat(scene))
+        if n == 0:
+            self.query_stats = abi.RtStats()
+            return out
+        with abi.DeviceScope(self.lib, self.ctx) as dev:
+            d_dir = dev.upload(d)
+            d_org = None if shared else dev.upload(o)
+            per_ray = isinstance(t, np.ndarray)
+            d_t = dev.upload(t) if per_ray else None
+            d_occ = dev.alloc(out.nbytes)
+            abi.check(self.lib, self._launch_occluded(n, d_org, o if shared else None, d_dir, d_t, 0.0 if per_ray else t,
+                                                      flags, d_occ, None))
+            self.query_stats, _ = abi.collect(self.lib, self.ctx)
+            dev.download(d_occ, out)
+        return out
+
+    def occluded_into(self, origins, directions, occluded, *, t_max=np.inf, stream=None, root2=False):
+        """rt_query_occluded_async on device arrays in place, without a copy: directions (n, 3) in the renderer's
+        precision and occluded (n,) uint8 are objects exposing __cuda_array_interface__ (torch ROCm tensors do),
+        C-contiguous, on the renderer's device.  origins: such an array of shape (n, 3), or 3 host numbers for one
+        shared origin.  t_max: a number (not NaN), or such an array of shape (n,) in the renderer's precision.  The
+        scene is the one last set (set_scene); stream as in query_into.  Returns the number of rays."""
+        flags = self._query_flags(root2)
+        n, d_org, origin, d_dir, d_t, t, d_occ = check_occluded_into(flags, self.device, origins, directions, occluded, t_max)
+        check_stream(stream)
+        check_scene_set(self._scene_flat)
+        abi.check(self.lib, self._launch_occluded(n, d_org, origin, d_dir, d_t, t, flags, d_occ, stream))
         return n
 
     def render_rays(self, max_bounces, spp, origins, directions, scene, seed=None, pixel_base=0, root2=False,
