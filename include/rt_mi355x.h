@@ -143,6 +143,12 @@ typedef struct rt_stats {
 /* Set: the occlusion kernel ran, occlusion_rays<T, ROOT2, MEGA> (rt_query_occluded_async); F64, WAVES, ROOT2 and MEGA
  * mean what they mean above, CAMQ, MODE, SPLIT, ITEMS, GUIDES, QUERY and RAYS are 0. */
 #define RT_KERNEL_OCCLUSION(id) (((id) >> 14) & 1u)
+/* Above bit 15.  Set: the scatter kernel ran, scatter_rays<T> (rt_scatter_async): F64 means what it means above, every
+ * other field is 0 (a map kernel without an occupancy target: WAVES is 0). */
+#define RT_KERNEL_SCATTER(id) (((id) >> 16) & 1u)
+/* Set: the fused path-step kernel ran, path_step_rays<T, ROOT2, MEGA> (rt_path_step_async); F64, WAVES, ROOT2 and MEGA
+ * mean what they mean above, every other field is 0. */
+#define RT_KERNEL_STEP(id) (((id) >> 17) & 1u)
 
 /* ---- flags ---- */
 #define RT_FLAG_F32 0x1u     /* compute in fp32 (default: fp64, the reference's arithmetic) */
@@ -350,6 +356,68 @@ int rt_query_hits_async(rt_context* ctx, uint64_t n_rays, const void* d_origins,
 int rt_query_occluded_async(rt_context* ctx, uint64_t n_rays, const void* d_origins, const double* origin,
                             const void* d_directions, const void* d_t_max, double t_max, uint32_t flags,
                             void* d_occluded, void* stream);
+/* ---- path steps: the material stage, for integrators the caller drives ----
+ * rt_query_hits_async says what a ray hits; these two produce the next ray and the attenuation, so that query ->
+ * scatter -> query is a path tracer whose loop, lights, outputs and termination rule belong to the caller (next-event
+ * estimation with rt_query_occluded_async, per-bounce outputs, ...).  T is float under RT_FLAG_F32, else double.
+ *
+ * rt_scatter_async: the material stage alone.  Per ray i with d_index[i] >= 0 it is exactly what a render does to a
+ * ray that hit sphere d_index[i] at parameter d_t[i] on bounce `bounce`:
+ *   PackedHitRecords::finalize (objects.rs:157-162): point o + d t, the normal with the packed length, front taken
+ *     before the negation; then Material::get_hit_result (materials.rs:54-147) with its one draw from stream 2 at
+ *     counter (d_sample[i], d_pixel[i], bounce), the keys derived from `seed` as rt_render_async derives them (the
+ *     fp32 fold included).
+ *   out origin: the hit point; out direction: the scattered direction, NOT normalised, as a render leaves it;
+ *   d_colour[i] *= attenuation, in place, component by component as the render multiplies (the albedo rounded to T
+ *     for Lambertian and Metal, 1 for Dielectric).
+ * A ray with d_index[i] < 0 (RT_QUERY_MISS, RT_QUERY_INVALID) is not scattered: its outputs are its inputs bit for
+ * bit and its colour is untouched.  No ray's values depend on another ray.
+ * Arguments: d_directions T [n][3]; the origins in rt_query_hits_async's two forms (exactly one); d_index int32 [n]
+ * and d_t T [n] as rt_query_hits_async writes them; d_pixel, d_sample uint32 [n]; d_colour T [n][3] or NULL (no
+ * colour is tracked); d_out_origins, d_out_directions T [n][3], one of them may be NULL; they may be the input arrays
+ * (in place) or separate ones, with identical values.
+ * d_index[i] >= n_spheres or d_sample[i] >= 2^20 (on a ray with d_index[i] >= 0): the ray is left as a miss is and
+ * rt_context_collect returns RT_ERR_INVALID; the other rays are untouched by it.
+ * flags: RT_FLAG_F32 and RT_FLAG_ROOT2 (the scatter does not depend on ROOT2).  Any RT_FLAG_MODE_* is
+ * RT_ERR_UNSUPPORTED; unknown bits are RT_ERR_INVALID.  RT_ERR_UNSUPPORTED: fp32 with bounce > RT_MAX_BOUNCES_F32
+ * (a render's own bounces end one below it; at RT_MAX_BOUNCES_F32 itself the fp32 counter's code wraps and the draw is
+ * stream 0's block of that sample), n_rays > 0x7FFFFFFF.  n_rays == 0: RT_OK, nothing is enqueued.  RT_ERR_INVALID, checked before any HIP call: ctx,
+ * d_directions, d_index, d_t, d_pixel or d_sample NULL, both output arrays NULL, both or neither origin form, no scene.
+ * rt_context_collect after it: pixels = n_rays, samples = the scattered rays, ray_segments = bounce_iters = 0,
+ * RT_KERNEL_SCATTER(kernel_id) is set.
+ *
+ * rt_path_step_async: closest hit and scatter in one kernel.  Per ray, bit for bit, what rt_query_hits_async followed
+ * by rt_scatter_async does on the same arrays in place, without the trip through memory between them:
+ *   a hit becomes the scattered ray (d_origins, d_directions and d_colour are updated);
+ *   a miss, and a ray outside the query's precondition (not traced), keep their origin, direction and colour: a
+ *   caller retires a ray by zeroing its direction.
+ * d_status uint8 [n]: RT_STEP_SCATTERED, RT_STEP_MISSED (not scattered) or RT_STEP_INVALID.  d_index, d_t, d_normal
+ * and d_front are rt_query_hits_async's outputs for the hit that was scattered (the hit point is the new origin; the
+ * normal is what a shadow ray or a BSDF weight needs).  Any of the five may be NULL and no value depends on which
+ * were asked for.  Origins are per ray only (the call writes them back); d_colour may be NULL.
+ * Flags, limits and the sample check are rt_scatter_async's.  RT_ERR_INVALID before any HIP call: ctx, d_origins,
+ * d_directions, d_pixel or d_sample NULL, no scene.
+ * rt_context_collect after it: pixels = n_rays, samples = ray_segments = the valid rays, bounce_iters = 0, lane_slots
+ * and the work counters as rt_query_hits_async counts them, RT_KERNEL_STEP(kernel_id) is set.
+ *
+ * The loop "colour = 1; for k < max_bounces: step; a miss multiplies by the sky of its own direction and retires; a
+ * ray alive at the end is 0" over a camera's primary rays (pixel = row W + col, sample = s), reduced as
+ * ((((0 + a0) + a1) + a2) + a3) / spp with a_l the sum over chunks j of sample 4 j + l, is bit for bit
+ * rt_render_async's linear output under RT_FLAG_MODE_VECTORIZED, as long as no scattered direction leaves the query's
+ * |d|^2 range (a render traces those too).
+ * Both calls are asynchronous on `stream` under rt_render_async's cross-stream rule and allowed while a progressive
+ * session is open.  Out of scope: compacting or sorting live rays between steps, a shared origin in the fused call,
+ * the scalar and vectorized* semantics. */
+#define RT_STEP_MISSED 0
+#define RT_STEP_SCATTERED 1
+#define RT_STEP_INVALID 255
+int rt_scatter_async(rt_context* ctx, uint64_t n_rays, const void* d_origins, const double* origin,
+                     const void* d_directions, const void* d_index, const void* d_t,
+                     const void* d_pixel, const void* d_sample, uint32_t bounce, uint64_t seed, uint32_t flags,
+                     void* d_colour, void* d_out_origins, void* d_out_directions, void* stream);
+int rt_path_step_async(rt_context* ctx, uint64_t n_rays, void* d_origins, void* d_directions, void* d_colour,
+                       const void* d_pixel, const void* d_sample, uint32_t bounce, uint64_t seed, uint32_t flags,
+                       void* d_status, void* d_index, void* d_t, void* d_normal, void* d_front, void* stream);
 /* ---- rendering caller-supplied primary rays: any camera model, full paths ----
  * rt_render_async with the primary rays taken from the caller's arrays instead of Camera::get_ray: an orthographic
  * view, a fisheye, a 360 degree panorama (rt_camera_rays below makes their rays) or the rays of the caller's own

@@ -31,7 +31,8 @@
 // layout and device code share; no HIP), rt_common.hpp (kernel arguments, scalar-load pipelines),
 // rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (the record view, replay + reduction),
 // rt_trace.hpp + rt_trace_body.hpp (the persistent kernel), rt_guides.hpp (guide buffers: first hits only),
-// rt_query.hpp (ray queries: the closest hit of the caller's rays, and occlusion before a t_max), rt_rays.hpp (full paths for the caller's
+// rt_query.hpp (ray queries: the closest hit of the caller's rays, and occlusion before a t_max),
+// rt_step.hpp (path steps: the material stage alone, and closest hit + scatter in one kernel), rt_rays.hpp (full paths for the caller's
 // primary rays); rt_projection.hpp (host only: the rays of camera models the reference lacks);
 // host only, without HIP: rt_layout.hpp (the scene image: every device table of a scene, build_scene_image),
 // rt_split_plan.hpp (the sample-parallel plan), rt_progressive_plan.hpp (a progressive session's record buffer,
@@ -41,7 +42,7 @@
 // launch_cam_table; it knows no context, and the test-only device library builds its arguments with it),
 // rt_launch.hpp (what a context's launches share, kernel selection and kernel_id, the launch steps frame_params,
 // ensure_cam_tables, frame_setup, plan_grid, and the launchers launch_plain, launch_split, launch_window,
-// launch_guides, launch_query, launch_occlusion, launch_rays), rt_session.hpp (a progressive session: its state, launch_items and launch_classes
+// launch_guides, launch_query, launch_occlusion, launch_scatter, launch_step, launch_rays), rt_session.hpp (a progressive session: its state, launch_items and launch_classes
 // for per-pixel counts, extend_uniform, run_map, snapshot_run and the steps of refine_step).  This file holds the
 // C ABI: rt_context, the entry points (their argument checks, then one call) and the small device helpers.
 #include "rt_session.hpp"
@@ -341,6 +342,59 @@ extern "C" int rt_query_occluded_async(rt_context* c, uint64_t n_rays, const voi
     return end_launch(c, st, n_rays, 0u);   // samples: the valid rays, counted on the device (kQuerySlot)
 }
 
+// The checks rt_scatter_async and rt_path_step_async share, after their own of the pointers.
+static int check_step(const rt_context* c, const std::string& who, uint64_t n_rays, uint32_t bounce, uint32_t flags) {
+    if (flags & ~RT_FLAG_ALL) return fail(RT_ERR_INVALID, who + ": unknown flag bits");
+    if (flags & ~(RT_FLAG_F32 | RT_FLAG_ROOT2))
+        return fail(RT_ERR_UNSUPPORTED, who + ": the live path only (RT_FLAG_F32, RT_FLAG_ROOT2; no RT_FLAG_MODE_*)");
+    if ((flags & RT_FLAG_F32) && bounce > RT_MAX_BOUNCES_F32)   // rng<float>'s counter (rt_device.hpp)
+        return fail(RT_ERR_UNSUPPORTED, who + ": fp32 with bounce > RT_MAX_BOUNCES_F32 (3839)");
+    if (n_rays > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many rays in one call");
+    if (!c->has_scene) return fail(RT_ERR_INVALID, who + ": no scene set (rt_context_set_scene first)");
+    return RT_OK;
+}
+
+extern "C" int rt_scatter_async(rt_context* c, uint64_t n_rays, const void* d_origins, const double* origin,
+                                const void* d_directions, const void* d_index, const void* d_t, const void* d_pixel,
+                                const void* d_sample, uint32_t bounce, uint64_t seed, uint32_t flags, void* d_colour,
+                                void* d_out_origins, void* d_out_directions, void* stream) {
+    const std::string who = "rt_scatter_async";
+    if (!c || !d_directions || !d_index || !d_t || !d_pixel || !d_sample)
+        return fail(RT_ERR_INVALID, who + ": NULL argument (ctx, d_directions, d_index, d_t, d_pixel or d_sample)");
+    if (!d_out_origins && !d_out_directions) return fail(RT_ERR_INVALID, who + ": both output arrays are NULL");
+    if ((d_origins != nullptr) == (origin != nullptr))
+        return fail(RT_ERR_INVALID, who + ": exactly one of d_origins (per ray) and origin (shared) must be given");
+    int rc = check_step(c, who, n_rays, bounce, flags);
+    if (rc != RT_OK) return rc;
+    if (n_rays == 0) return RT_OK;
+    const ScatterArgs a{n_rays, d_origins, origin, d_directions, d_index, d_t, d_pixel, d_sample, bounce, seed, flags,
+                        d_colour, d_out_origins, d_out_directions};
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = begin_launch(c, st)) != RT_OK) return rc;
+    rc = with_precision((flags & RT_FLAG_F32) != 0, [&](auto t) { return launch_scatter<decltype(t)>(c, a, st); });
+    if (rc != RT_OK) return rc;
+    return end_launch(c, st, n_rays, 0u);   // samples: the scattered rays, counted on the device (kQuerySlot)
+}
+
+extern "C" int rt_path_step_async(rt_context* c, uint64_t n_rays, void* d_origins, void* d_directions, void* d_colour,
+                                  const void* d_pixel, const void* d_sample, uint32_t bounce, uint64_t seed,
+                                  uint32_t flags, void* d_status, void* d_index, void* d_t, void* d_normal, void* d_front,
+                                  void* stream) {
+    const std::string who = "rt_path_step_async";
+    if (!c || !d_origins || !d_directions || !d_pixel || !d_sample)
+        return fail(RT_ERR_INVALID, who + ": NULL argument (ctx, d_origins, d_directions, d_pixel or d_sample)");
+    int rc = check_step(c, who, n_rays, bounce, flags);
+    if (rc != RT_OK) return rc;
+    if (n_rays == 0) return RT_OK;
+    const StepArgs a{n_rays, d_origins, d_directions, d_colour, d_pixel, d_sample, bounce, seed, flags,
+                     d_status, d_index, d_t, d_normal, d_front};
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = begin_launch(c, st)) != RT_OK) return rc;
+    rc = with_precision((flags & RT_FLAG_F32) != 0, [&](auto t) { return launch_step<decltype(t)>(c, a, st); });
+    if (rc != RT_OK) return rc;
+    return end_launch(c, st, n_rays, 0u);   // samples: the valid rays, counted on the device (kQuerySlot)
+}
+
 extern "C" int rt_render_rays_async(rt_context* c, uint64_t n_pixels, uint32_t spp, uint32_t rays_per_pixel,
                                     const void* d_origins, const double* origin, const void* d_directions,
                                     uint32_t max_bounces, uint64_t seed, uint32_t pixel_base, uint32_t flags,
@@ -583,9 +637,10 @@ extern "C" int rt_context_collect(rt_context* c, void* stream, rt_stats* out) {
     hipStream_t st = (hipStream_t)stream;   // NULL = the HIP null stream
     HIPCHK(hipStreamSynchronize(st));
     std::vector<unsigned long long> segs(kSegShards * kSegStride);
-    uint32_t err = 0;
+    uint32_t errs[2] = {0u, 0u};   // word 0: a pixel channel above 2.0 (finish); word 1: a path step's ray outside its contract
     HIPCHK(hipMemcpy(segs.data(), c->segs.p, segs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&err, c->err.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(errs, c->err.p, sizeof(errs), hipMemcpyDeviceToHost));
+    const uint32_t err = errs[0];
     float ms = 0.f;
     if (c->have_first) HIPCHK(hipEventElapsedTime(&ms, c->ev_first, c->ev_last));
     HIPCHK(hipMemset(c->segs.p, 0, segs.size() * sizeof(unsigned long long)));
@@ -633,6 +688,9 @@ extern "C" int rt_context_collect(rt_context* c, void* stream, rt_stats* out) {
     c->have_first = false;
     c->pixels = c->samples = 0;
     c->last_kernel_id = c->last_wg_per_cu = 0;
+    if (errs[1])
+        return fail(RT_ERR_INVALID, "rt_scatter_async / rt_path_step_async: a ray with index >= n_spheres or sample >= 2^20 "
+                                    "(not scattered; the other rays are as they would be without it)");
     if (err) return fail(RT_ERR_RANGE, "a pixel channel exceeded 2.0 (Color::to_u8_array would panic, color.rs:55-57)");
     return RT_OK;
 }

@@ -1,11 +1,13 @@
 // rt_launch.hpp — the launches of the C ABI, host only: what the launches of a context share (LaunchContext),
 // the kernel selection and rt_stats.kernel_id, the steps of a launch (context_params, frame_params,
 // ensure_cam_tables, frame_setup, plan_grid) and the launchers (launch_plain, launch_split, launch_window,
-// launch_guides, launch_query, launch_occlusion, launch_rays), between begin_launch and end_launch.
+// launch_guides, launch_query, launch_occlusion, launch_scatter, launch_step, launch_rays), between begin_launch and
+// end_launch.
 #pragma once
 #include "rt_trace.hpp"
 #include "rt_guides.hpp"
 #include "rt_query.hpp"
+#include "rt_step.hpp"
 #include "rt_rays.hpp"
 #include "rt_host.hpp"
 #include "rt_split_plan.hpp"
@@ -48,6 +50,8 @@ constexpr uint32_t kKernelGuidesBit = 1u << 11;   // guide_pixels
 constexpr uint32_t kKernelQueryBit = 1u << 12;    // query_rays (its SHARED takes the camera-batch bit)
 constexpr uint32_t kKernelRaysBit = 1u << 13;     // trace_paths_rays
 constexpr uint32_t kKernelOcclusionBit = 1u << 14;   // occlusion_rays
+constexpr uint32_t kKernelScatterBit = 1u << 16;   // scatter_rays (bit 15: any kernel)
+constexpr uint32_t kKernelStepBit = 1u << 17;      // path_step_rays
 template <typename T>
 constexpr uint32_t kernel_id(int W, bool root2, int mode, bool camq, bool mega, uint32_t family) {
     return 0x8000u | (sizeof(T) == 8 ? 1u : 0u) | ((uint32_t)W << 1) | (root2 ? kKernelRoot2Bit : 0u) |
@@ -138,6 +142,11 @@ template <typename T>
 static void (*pick_occlusion(bool root2, bool mega))(OParams<T>) {
     return with_bools([](auto r2, auto mg) { return occlusion_rays<T, r2.value, mg.value>; }, root2, mega);
 }
+// The fused path-step kernel (rt_path_step_async): path_step_rays<T, ROOT2, MEGA>.
+template <typename T>
+static void (*pick_step(bool root2, bool mega))(PsParams<T>) {
+    return with_bools([](auto r2, auto mg) { return path_step_rays<T, r2.value, mg.value>; }, root2, mega);
+}
 // The caller-ray kernel (rt_render_rays_async): trace_paths_rays<T, W, ROOT2, MEGA> at the precision's default W.
 template <typename T>
 static void (*pick_rays(bool root2, bool mega))(RParams<T>) {
@@ -187,6 +196,15 @@ static void context_params(LaunchContext* c, bool filter_off, KParams<T>& p) {
     p.counter = (uint32_t*)c->counter.p;
 }
 
+// The RNG key of a seed.  fp64: Philox4x32-10 keyed by (seed lo, seed hi).  fp32: Philox2x32-10 has a 32-bit key,
+// folded here as seed lo ^ fmix32(seed hi) (rng<float> reads k0 only): fmix32(0) = 0, so a seed below 2^32 keys as
+// itself, and seeds such as (m << 32) | m no longer all key as 0.
+template <typename T>
+static void key_params(uint64_t seed, KParams<T>& p) {
+    if (sizeof(T) == 8) { p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32); }
+    else { p.k0 = (uint32_t)seed ^ fmix32((uint32_t)(seed >> 32)); p.k1 = 0u; }
+}
+
 // The camera, the sample counts, the RNG key, the tile range and the outputs; n_items: one per pixel.
 template <typename T>
 static void frame_params(const FrameArgs& a, KParams<T>& p) {
@@ -212,11 +230,7 @@ static void frame_params(const FrameArgs& a, KParams<T>& p) {
         if (pinhole) p.flags |= kFlagPinholeInternal;
     }
     p.s_sel = (p.C - 1) % 2;   // ray_tracing.rs:486
-    // fp64: Philox4x32-10 keyed by (seed lo, seed hi).  fp32: Philox2x32-10 has a 32-bit key, folded here as
-    // seed lo ^ fmix32(seed hi) (rng<float> reads k0 only): fmix32(0) = 0, so a seed below 2^32 keys as itself,
-    // and seeds such as (m << 32) | m no longer all key as 0.
-    if (sizeof(T) == 8) { p.k0 = (uint32_t)a.seed; p.k1 = (uint32_t)(a.seed >> 32); }
-    else { p.k0 = (uint32_t)a.seed ^ fmix32((uint32_t)(a.seed >> 32)); p.k1 = 0u; }
+    key_params(a.seed, p);
     const rt_tile_range& rg = a.rg;
     p.row_begin = rg.row_begin; p.row_step = rg.row_step; p.col_begin = rg.col_begin; p.col_count = rg.col_count;
     p.rgb = (uint8_t*)a.rgb;
@@ -458,6 +472,95 @@ static int launch_occlusion(LaunchContext* c, const OcclusionArgs& a, hipStream_
     op.t_max_all = (T)a.t_max;
     op.occluded = (uint8_t*)a.occluded;
     hipLaunchKernelGGL(ofn, dim3((uint32_t)nblocks), dim3(256), 0, st, op);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// What rt_scatter_async asks for: a query's rays and its index and t, the draw's counter (pixel, sample, bounce) and
+// seed, the colour (in place, may be NULL) and the scattered rays (may be the inputs).
+struct ScatterArgs {
+    uint64_t n_rays;
+    const void* origins;
+    const double* origin;
+    const void* directions;
+    const void *index, *t, *pixel, *sample;
+    uint32_t bounce;
+    uint64_t seed;
+    uint32_t flags;
+    void *colour, *out_origins, *out_directions;
+};
+
+// scatter_rays: a map kernel, one thread per ray.  No sweep: of the scene it reads the centre and material tables.
+// The key is a render's (key_params); a shared origin is rounded as a camera centre is and broadcast by the kernel.
+template <typename T>
+static int launch_scatter(LaunchContext* c, const ScatterArgs& a, hipStream_t st) {
+    ScParams<T> sp;
+    memset(&sp, 0, sizeof(sp));
+    context_params(c, filter_off_env(), sp.k);
+    sp.k.flags = a.flags;
+    sp.k.n_items = (uint32_t)a.n_rays;
+    key_params(a.seed, sp.k);
+    if (a.origin) for (int i = 0; i < 3; ++i) sp.k.center[i] = (T)a.origin[i];
+    sp.origins = (const T*)a.origins;
+    sp.directions = (const T*)a.directions;
+    sp.index = (const int32_t*)a.index;
+    sp.t = (const T*)a.t;
+    sp.pixel = (const uint32_t*)a.pixel;
+    sp.sample = (const uint32_t*)a.sample;
+    sp.bounce = a.bounce;
+    sp.colour = (T*)a.colour;
+    sp.out_origins = (T*)a.out_origins;
+    sp.out_directions = (T*)a.out_directions;
+    c->last_kernel_id = kernel_id<T>(0, false, kModeV2, false, false, kKernelScatterBit);   // no occupancy target: W 0
+    c->last_wg_per_cu = 0;
+    hipLaunchKernelGGL(scatter_rays<T>, dim3((uint32_t)((a.n_rays + 255u) / 256u)), dim3(256), 0, st, sp);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// What rt_path_step_async asks for: the rays and the colour (updated in place), the draw's counter and seed, and the
+// outputs (any may be NULL).
+struct StepArgs {
+    uint64_t n_rays;
+    void *origins, *directions, *colour;
+    const void *pixel, *sample;
+    uint32_t bounce;
+    uint64_t seed;
+    uint32_t flags;
+    void *status, *index, *t, *normal, *front;
+};
+
+// path_step_rays: launch_query's grid for rays with origins of their own (the general sweep: no camera tables).
+template <typename T>
+static int launch_step(LaunchContext* c, const StepArgs& a, hipStream_t st) {
+    KParams<T> p;
+    context_params(c, filter_off_env(), p);
+    p.flags = a.flags;
+    p.n_items = (uint32_t)a.n_rays;
+    key_params(a.seed, p);
+    const bool root2 = (a.flags & RT_FLAG_ROOT2) != 0u, mega = p.n_mg > 0;
+    void (*const sfn)(PsParams<T>) = pick_step<T>(root2, mega);
+    constexpr int W = kWavesQuery<T>;
+    const uint32_t id = kernel_id<T>(W, root2, kModeV2, false, mega, kKernelStepBit);
+    const uint32_t n_batches = (uint32_t)((a.n_rays + 63u) / 64u);   // a wave's work item
+    uint64_t nblocks = 0;
+    const int rc = plan_grid(c, (const void*)sfn, W, id, n_batches, 1u, nblocks, p.blk_g);
+    if (rc != RT_OK) return rc;
+    PsParams<T> pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.k = p;
+    pp.origins = (T*)a.origins;
+    pp.directions = (T*)a.directions;
+    pp.colour = (T*)a.colour;
+    pp.pixel = (const uint32_t*)a.pixel;
+    pp.sample = (const uint32_t*)a.sample;
+    pp.bounce = a.bounce;
+    pp.status = (uint8_t*)a.status;
+    pp.index = (int32_t*)a.index;
+    pp.t = (T*)a.t;
+    pp.normal = (T*)a.normal;
+    pp.front = (uint8_t*)a.front;
+    hipLaunchKernelGGL(sfn, dim3((uint32_t)nblocks), dim3(256), 0, st, pp);
     HIPCHK(hipGetLastError());
     return RT_OK;
 }

@@ -116,11 +116,24 @@ def RT_KERNEL_OCCLUSION(kernel_id):
     return (kernel_id >> 14) & 1
 
 
+def RT_KERNEL_SCATTER(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_SCATTER: the scatter kernel ran (rt_scatter_async)."""
+    return (kernel_id >> 16) & 1
+
+
+def RT_KERNEL_STEP(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_STEP: the fused path-step kernel ran (rt_path_step_async)."""
+    return (kernel_id >> 17) & 1
+
+
 RT_QUERY_MISS = -1      # include/rt_mi355x.h: rt_query_hits_async's index of a ray that hits nothing
 RT_QUERY_INVALID = -2   # ... and of a ray outside the precondition (not traced)
 RT_OCCLUDED_NO = 0          # include/rt_mi355x.h: rt_query_occluded_async's byte of a ray with nothing before its t_max,
 RT_OCCLUDED_YES = 1         # ... of a ray with an accepted root below its t_max,
 RT_OCCLUDED_INVALID = 255   # ... and of a ray outside the precondition or with a NaN t_max (not traced)
+RT_STEP_MISSED = 0        # include/rt_mi355x.h: rt_path_step_async's status of a ray that was not scattered,
+RT_STEP_SCATTERED = 1     # ... of a ray that hit and became its scattered ray,
+RT_STEP_INVALID = 255     # ... and of a ray outside the query's precondition (not traced)
 
 
 def kernel_info(kernel_id):
@@ -131,7 +144,8 @@ def kernel_info(kernel_id):
             "mode": (kernel_id >> 5) & 3, "camq": bool((kernel_id >> 7) & 1), "mega": bool((kernel_id >> 8) & 1),
             "split": bool(RT_KERNEL_SPLIT(kernel_id)), "items": bool(RT_KERNEL_ITEMS(kernel_id)),
             "guides": bool(RT_KERNEL_GUIDES(kernel_id)), "query": bool(RT_KERNEL_QUERY(kernel_id)),
-            "rays": bool(RT_KERNEL_RAYS(kernel_id)), "occlusion": bool(RT_KERNEL_OCCLUSION(kernel_id))}
+            "rays": bool(RT_KERNEL_RAYS(kernel_id)), "occlusion": bool(RT_KERNEL_OCCLUSION(kernel_id)),
+            "scatter": bool(RT_KERNEL_SCATTER(kernel_id)), "step": bool(RT_KERNEL_STEP(kernel_id))}
 
 
 def kernel_name(kernel_id):
@@ -140,6 +154,10 @@ def kernel_name(kernel_id):
     if k is None:
         return None
     b = lambda v: "true" if v else "false"
+    if k["step"]:   # path_step_rays<T,ROOT2,MEGA>
+        return f"path_step_rays<{k['T']},{b(k['root2'])},{b(k['mega'])}>"
+    if k["scatter"]:   # scatter_rays<T>
+        return f"scatter_rays<{k['T']}>"
     if k["occlusion"]:   # occlusion_rays<T,ROOT2,MEGA>
         return f"occlusion_rays<{k['T']},{b(k['root2'])},{b(k['mega'])}>"
     if k["rays"]:   # trace_paths_rays<T,W,ROOT2,MEGA> (rays_validate<T> runs ahead of it)
@@ -184,7 +202,7 @@ EXPORTED = [
     "rt_progressive_extend_map_async", "rt_progressive_snapshot_map_async", "rt_progressive_counts",
     "rt_progressive_error_async", "rt_progressive_map_plan", "rt_progressive_refine", "rt_progressive_refine_items",
     "rt_render_guides_async", "rt_query_hits_async", "rt_memcpy_h2d", "rt_render_rays_async", "rt_camera_rays",
-    "rt_query_occluded_async",
+    "rt_query_occluded_async", "rt_scatter_async", "rt_path_step_async",
 ]
 
 _lib = None
@@ -192,7 +210,7 @@ _lib = None
 # The sources the Makefile hashes into rt_version() ("src=<hash>"), in its order (SRC, then HDR).
 KERNEL_SOURCES = ["rt_kernel.hip", "rt_experiments.hpp", "rt_formats.hpp", "rt_common.hpp", "rt_sweep.hpp",
                   "rt_camera.hpp", "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_rays.hpp", "rt_projection.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp",
-                  "rt_progressive_plan.hpp", "rt_host.hpp", "rt_launch.hpp", "rt_session.hpp", "rt_guides.hpp", "rt_query.hpp"]
+                  "rt_progressive_plan.hpp", "rt_host.hpp", "rt_launch.hpp", "rt_session.hpp", "rt_guides.hpp", "rt_step.hpp", "rt_query.hpp"]
 SOURCE_FILES = [os.path.join(PKG_DIR, "csrc", f) for f in KERNEL_SOURCES] + \
                [os.path.join(os.path.dirname(PKG_DIR), "include", "rt_mi355x.h")]
 
@@ -248,6 +266,8 @@ def load_library(path=None):
     lib.rt_render_guides_async.argtypes = [vp, P(RtCamera), u32, u64, u32, P(RtTileRange), vp, vp, vp, vp, vp]
     lib.rt_query_hits_async.argtypes = [vp, u64, vp, P(f64), vp, u32, vp, vp, vp, vp, vp, vp]
     lib.rt_query_occluded_async.argtypes = [vp, u64, vp, P(f64), vp, vp, f64, u32, vp, vp]
+    lib.rt_scatter_async.argtypes = [vp, u64, vp, P(f64), vp, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, vp]
+    lib.rt_path_step_async.argtypes = [vp, u64, vp, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, vp, vp, vp]
     lib.rt_render_rays_async.argtypes = [vp, u64, u32, u32, vp, P(f64), vp, u32, u64, u32, u32, vp, vp, vp]
     lib.rt_camera_rays.argtypes = [P(RtProjection), u32, u32, vp, vp]
     lib.rt_split_plan.argtypes = [u64, u32, u32, P(u32), P(u64)]

@@ -22,6 +22,9 @@ from .checks import (ADAPTIVE_PLANS, GUIDE_CHANNELS, GUIDE_NAMES, QUERY_NAMES, Q
                      _device_array, _query_shape, check_adaptive, check_guides, check_query, check_query_into,
                      check_render_rays, check_render_rays_into, check_schedule, check_stream, split_argument)
 from .occlusion_checks import check_occluded, check_occluded_into, check_scene_set  # noqa: F401
+from .step_checks import (STEP_NAMES, STEP_OUTPUTS, _step_shape, check_path_step, check_path_step_into,  # noqa: F401
+                          check_scatter, check_scatter_into, check_seed, check_step_names)
+from .step_checks import check_scene_set as check_step_scene
 
 
 class RenderStat:
@@ -458,6 +461,119 @@ class GpuRenderer(Renderer):
         check_stream(stream)
         check_scene_set(self._scene_flat)
         abi.check(self.lib, self._launch_occluded(n, d_org, origin, d_dir, d_t, t, flags, d_occ, stream))
+        return n
+
+    def _launch_scatter(self, n, d_org, origin, d_dir, d_idx, d_t, d_pix, d_smp, bounce, seed, flags, d_col, d_oo, d_od,
+                        stream):
+        return self.lib.rt_scatter_async(self.ctx, n, d_org, _pointer(origin, abi.f64), d_dir, d_idx, d_t, d_pix, d_smp,
+                                         bounce, self.seed if seed is None else seed, flags, d_col, d_oo, d_od, stream)
+
+    def _launch_step(self, n, d_org, d_dir, d_col, d_pix, d_smp, bounce, seed, flags, ptrs, stream):
+        return self.lib.rt_path_step_async(self.ctx, n, d_org, d_dir, d_col, d_pix, d_smp, bounce,
+                                           self.seed if seed is None else seed, flags,
+                                           *[ptrs.get(name) for name in STEP_NAMES], stream)
+
+    def scatter(self, origins, directions, index, t, scene, pixel=None, sample=None, bounce=0, colour=None, seed=None,
+                root2=False):
+        """rt_scatter_async with numpy arrays: the material stage of a render for rays whose hits are known
+        (include/rt_mi355x.h has the definition).  origins, directions: as query() takes them; index, t: as query()
+        returns them; pixel, sample: (n,) integers, the counter of each ray's draw (None: arange(n) and zeros); bounce:
+        the draw's bounce; colour: (n, 3) or None; seed: the RNG key (None: the renderer's).
+        Returns {"origins": (n, 3), "directions": (n, 3), "colour": (n, 3) | None}: a ray with index >= 0 as its
+        scattered ray (origin the hit point, direction not normalised, colour times the attenuation), any other ray as
+        it came.  The call's RtStats are kept in self.query_stats."""
+        flags = self._query_flags(root2)
+        o, d, shared, i, tt, pix, smp, col, bounce = check_scatter(flags, origins, directions, index, t, pixel, sample,
+                                                                    colour, bounce)   # before any GPU call
+        seed = check_seed(seed)
+        n = d.shape[0]
+        out = {"origins": np.empty((n, 3), dtype=d.dtype), "directions": np.empty((n, 3), dtype=d.dtype), "colour": col}
+        self._use_scene(_flat(scene))
+        if n == 0:
+            self.query_stats = abi.RtStats()
+            return out
+        with abi.DeviceScope(self.lib, self.ctx) as dev:
+            d_dir = dev.upload(d)
+            d_org = None if shared else dev.upload(o)
+            d_col = None if col is None else dev.upload(col)
+            d_oo = dev.alloc(d.nbytes) if shared else d_org
+            abi.check(self.lib, self._launch_scatter(n, d_org, o if shared else None, d_dir, dev.upload(i), dev.upload(tt),
+                                                     dev.upload(pix), dev.upload(smp), bounce, seed, flags, d_col, d_oo,
+                                                     d_dir, None))
+            self.query_stats, _ = abi.collect(self.lib, self.ctx)
+            dev.download(d_oo, out["origins"])
+            dev.download(d_dir, out["directions"])
+            if col is not None:
+                dev.download(d_col, col)
+        return out
+
+    def scatter_into(self, origins, directions, index, t, pixel, sample, *, bounce=0, colour=None, out_origins=None,
+                     out_directions=None, seed=None, stream=None, root2=False):
+        """rt_scatter_async on device arrays, without a copy: directions (n, 3), index (n,) int32, t (n,), pixel and
+        sample (n,) uint32 and colour (n, 3) (or None) are objects exposing __cuda_array_interface__ (torch ROCm tensors
+        do), C-contiguous, on the renderer's device, the reals in the renderer's precision.  origins: such an array of
+        shape (n, 3), or 3 host numbers for one shared origin.  out_origins, out_directions: where the scattered rays
+        go; None: in place (with a shared origin: out_origins = None writes no origins).  colour is updated in place.
+        The scene is the one last set (set_scene); stream as in query_into.  Returns the number of rays."""
+        flags = self._query_flags(root2)
+        n, d_org, origin, d_dir, d_idx, d_t, d_pix, d_smp, d_col, d_oo, d_od, bounce = check_scatter_into(
+            flags, self.device, origins, directions, index, t, pixel, sample, colour, out_origins, out_directions, bounce)
+        seed = check_seed(seed)
+        check_stream(stream)
+        check_step_scene(self._scene_flat, "scatter_into")
+        abi.check(self.lib, self._launch_scatter(n, d_org, origin, d_dir, d_idx, d_t, d_pix, d_smp, bounce, seed, flags,
+                                                 d_col, d_oo, d_od, stream))
+        return n
+
+    def path_step(self, origins, directions, scene, pixel=None, sample=None, bounce=0, colour=None, seed=None,
+                  root2=False, want=STEP_NAMES):
+        """rt_path_step_async with numpy arrays: the closest hit of each ray and its scatter in one kernel
+        (include/rt_mi355x.h has the definition).  origins, directions: (n, 3); pixel, sample, bounce, colour, seed as in
+        scatter().  Returns a dict: "origins", "directions" (n, 3) and "colour" ((n, 3) | None) after the step (a hit as
+        its scattered ray; a miss and an invalid ray as they came), and for the names in `want`: status (n,) uint8
+        (abi.RT_STEP_SCATTERED, RT_STEP_MISSED, RT_STEP_INVALID) and the query's index, t, normal and front of the hit
+        that was scattered.  The call's RtStats are kept in self.query_stats."""
+        flags = self._query_flags(root2)
+        o, d, pix, smp, col, bounce = check_path_step(flags, origins, directions, pixel, sample, colour, bounce)
+        seed = check_seed(seed)
+        want = check_step_names(want)
+        n = d.shape[0]
+        out = {"origins": o, "directions": d, "colour": col}
+        out.update({name: np.empty(_step_shape(name, n), dtype=STEP_OUTPUTS[name][1] or d.dtype) for name in want})
+        self._use_scene(_flat(scene))
+        if n == 0:
+            self.query_stats = abi.RtStats()
+            return out
+        with abi.DeviceScope(self.lib, self.ctx) as dev:
+            d_org, d_dir = dev.upload(o), dev.upload(d)
+            d_col = None if col is None else dev.upload(col)
+            ptrs = {name: dev.alloc(out[name].nbytes) for name in want}
+            abi.check(self.lib, self._launch_step(n, d_org, d_dir, d_col, dev.upload(pix), dev.upload(smp), bounce, seed,
+                                                  flags, ptrs, None))
+            self.query_stats, _ = abi.collect(self.lib, self.ctx)
+            dev.download(d_org, o)
+            dev.download(d_dir, d)
+            if col is not None:
+                dev.download(d_col, col)
+            for name in want:
+                dev.download(ptrs[name], out[name])
+        return out
+
+    def path_step_into(self, origins, directions, pixel, sample, *, bounce=0, colour=None, status=None, index=None,
+                       t=None, normal=None, front=None, seed=None, stream=None, root2=False):
+        """rt_path_step_async on device arrays in place, without a copy: origins and directions (n, 3) and colour
+        (n, 3) (or None) are updated; pixel and sample are (n,) uint32; status (n,) uint8, index (n,) int32, t (n,),
+        normal (n, 3) and front (n,) uint8 are optional outputs.  All are objects exposing __cuda_array_interface__
+        (torch ROCm tensors do), C-contiguous, on the renderer's device, the reals in the renderer's precision.  The
+        scene is the one last set (set_scene); stream as in query_into.  Returns the number of rays."""
+        flags = self._query_flags(root2)
+        n, d_org, d_dir, d_col, d_pix, d_smp, ptrs, bounce = check_path_step_into(
+            flags, self.device, origins, directions, pixel, sample, colour,
+            dict(status=status, index=index, t=t, normal=normal, front=front), bounce)
+        seed = check_seed(seed)
+        check_stream(stream)
+        check_step_scene(self._scene_flat, "path_step_into")
+        abi.check(self.lib, self._launch_step(n, d_org, d_dir, d_col, d_pix, d_smp, bounce, seed, flags, ptrs, stream))
         return n
 
     def render_rays(self, max_bounces, spp, origins, directions, scene, seed=None, pixel_base=0, root2=False,
