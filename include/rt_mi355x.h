@@ -149,6 +149,11 @@ typedef struct rt_stats {
 /* Set: the fused path-step kernel ran, path_step_rays<T, ROOT2, MEGA> (rt_path_step_async); F64, WAVES, ROOT2 and MEGA
  * mean what they mean above, every other field is 0. */
 #define RT_KERNEL_STEP(id) (((id) >> 17) & 1u)
+/* Set together with RT_KERNEL_STEP: the list step ran, path_step_list<T, ROOT2, MEGA> (rt_path_step_list_async; the
+ * compaction kernels follow it where an output list was asked for); F64, WAVES, ROOT2 and MEGA are the step's.  Set
+ * alone: a list compaction ran (rt_ray_list_compact_async: keep_ballots, list_tile_sums, list_scan_tiles,
+ * list_scatter), kernels without a precision or an occupancy target: F64 and WAVES are 0. */
+#define RT_KERNEL_LIST(id) (((id) >> 18) & 1u)
 
 /* ---- flags ---- */
 #define RT_FLAG_F32 0x1u     /* compute in fp32 (default: fp64, the reference's arithmetic) */
@@ -406,8 +411,8 @@ int rt_query_occluded_async(rt_context* ctx, uint64_t n_rays, const void* d_orig
  * rt_render_async's linear output under RT_FLAG_MODE_VECTORIZED, as long as no scattered direction leaves the query's
  * |d|^2 range (a render traces those too).
  * Both calls are asynchronous on `stream` under rt_render_async's cross-stream rule and allowed while a progressive
- * session is open.  Out of scope: compacting or sorting live rays between steps, a shared origin in the fused call,
- * the scalar and vectorized* semantics. */
+ * session is open.  Out of scope: sorting live rays between steps (compacting them: the ray lists below), a shared
+ * origin in the fused call, the scalar and vectorized* semantics. */
 #define RT_STEP_MISSED 0
 #define RT_STEP_SCATTERED 1
 #define RT_STEP_INVALID 255
@@ -418,6 +423,51 @@ int rt_scatter_async(rt_context* ctx, uint64_t n_rays, const void* d_origins, co
 int rt_path_step_async(rt_context* ctx, uint64_t n_rays, void* d_origins, void* d_directions, void* d_colour,
                        const void* d_pixel, const void* d_sample, uint32_t bounce, uint64_t seed, uint32_t flags,
                        void* d_status, void* d_index, void* d_t, void* d_normal, void* d_front, void* stream);
+/* ---- ray lists: path steps over the live rays only, compacted on the device ----
+ * A ray list is a device array uint32_t list[n_rays] of ray ids plus a device word uint32_t count: the first count
+ * entries are the list, entries past count are never read.  The ray arrays (d_origins, d_directions, d_colour, d_pixel,
+ * d_sample and every output) stay where they are and are indexed by ray id; only the list shrinks.
+ *
+ * rt_path_step_list_async: for each listed ray r = list_in[i], i < count, exactly what rt_path_step_async does to ray
+ * r, bit for bit: the ray, the colour, d_status[r] and the optional d_index[r], d_t[r], d_normal[r], d_front[r].
+ * No byte of any array is written at a ray that is not listed: a retired ray keeps its final direction, colour and last
+ * status (RT_STEP_MISSED, RT_STEP_SCATTERED, RT_STEP_INVALID) for the caller to read once at the end.
+ * d_list_in NULL: the identity list 0 .. n_rays - 1.  d_count_in NULL: count = n_rays (both NULL: a first step needs
+ * no list).  d_list_out and d_count_out, given together or both NULL (no output list): list_out receives list_in[i]
+ * for every i whose ray reported RT_STEP_SCATTERED, in increasing i (stable order: an increasing list stays increasing,
+ * and the list is reproducible byte for byte), and *count_out how many.  Words of list_out past *count_out are not
+ * written.
+ *
+ * rt_ray_list_compact_async: the same selection under the caller's own rule: entry i is kept iff
+ * d_keep[list_in[i]] != 0 (d_keep uint8 [n_rays], by ray id): Russian roulette, a throughput cut-off, or a list built
+ * from a status array (d_list_in NULL, d_keep = d_status).
+ *
+ * Lists: a list entry >= n_rays is skipped (no ray is touched for it, it is never in list_out), a count > n_rays is
+ * clamped to n_rays; either sets the error word rt_scatter_async's sample check sets, so rt_context_collect returns
+ * RT_ERR_INVALID.  The kernels check these bounds and never fault on a bad list.  A ray id listed twice is undefined
+ * for that ray only.
+ * RT_ERR_INVALID before any HIP call: d_list_out == d_list_in or d_count_out == d_count_in when both are non-NULL
+ * (callers ping-pong two lists and two counts); exactly one of d_list_out and d_count_out given; d_keep NULL; a
+ * compaction with no output list; and for the step rt_path_step_async's own (ctx, d_origins, d_directions, d_pixel or
+ * d_sample NULL, no scene).  Flags, limits and the sample check are rt_path_step_async's: n_rays == 0: RT_OK, nothing
+ * is enqueued; n_rays > 0x7FFFFFFF: RT_ERR_UNSUPPORTED; any RT_FLAG_MODE_*: RT_ERR_UNSUPPORTED.
+ * Both calls are asynchronous on `stream` under rt_render_async's cross-stream rule and allowed while a progressive
+ * session is open; several may be enqueued and collected once, and no call reads the count on the host.  The
+ * compaction's scratch (a 64-bit word per 64 list positions, a word per tile) belongs to the context and only grows.
+ * Environment RT_LIST_TILE (64 .. 65536, a power of two; read at every call, any other value ignored): the rays per
+ * tile of the compaction's scan, default 65536.  It changes no result.
+ * rt_context_collect after them: pixels = n_rays per call; a step's samples = ray_segments = the valid listed rays,
+ * lane_slots and the work counters as rt_path_step_async counts them; a compaction counts nothing.
+ * RT_KERNEL_LIST(kernel_id) is set, together with RT_KERNEL_STEP by a step.
+ * Out of scope: occlusion queries and rt_scatter_async over a list, sorting or binning a list, moving the ray arrays. */
+int rt_path_step_list_async(rt_context* ctx, uint64_t n_rays, const void* d_list_in, const void* d_count_in,
+                            void* d_origins, void* d_directions, void* d_colour, const void* d_pixel, const void* d_sample,
+                            uint32_t bounce, uint64_t seed, uint32_t flags,
+                            void* d_status, void* d_index, void* d_t, void* d_normal, void* d_front,
+                            void* d_list_out, void* d_count_out, void* stream);
+int rt_ray_list_compact_async(rt_context* ctx, uint64_t n_rays, const void* d_list_in, const void* d_count_in,
+                              const void* d_keep /* uint8 [n_rays], by ray id */,
+                              void* d_list_out, void* d_count_out, void* stream);
 /* ---- rendering caller-supplied primary rays: any camera model, full paths ----
  * rt_render_async with the primary rays taken from the caller's arrays instead of Camera::get_ray: an orthographic
  * view, a fisheye, a 360 degree panorama (rt_camera_rays below makes their rays) or the rays of the caller's own

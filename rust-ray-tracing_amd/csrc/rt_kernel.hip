@@ -32,7 +32,8 @@
 // rt_sweep.hpp (general sweep), rt_camera.hpp (primary rays, scatter), rt_finish.hpp (the record view, replay + reduction),
 // rt_trace.hpp + rt_trace_body.hpp (the persistent kernel), rt_guides.hpp (guide buffers: first hits only),
 // rt_query.hpp (ray queries: the closest hit of the caller's rays, and occlusion before a t_max),
-// rt_step.hpp (path steps: the material stage alone, and closest hit + scatter in one kernel), rt_rays.hpp (full paths for the caller's
+// rt_step.hpp (path steps: the material stage alone, and closest hit + scatter in one kernel), rt_list.hpp (ray lists:
+// the step over the live rays only, and the stable compaction that leaves the next list), rt_rays.hpp (full paths for the caller's
 // primary rays); rt_projection.hpp (host only: the rays of camera models the reference lacks);
 // host only, without HIP: rt_layout.hpp (the scene image: every device table of a scene, build_scene_image),
 // rt_split_plan.hpp (the sample-parallel plan), rt_progressive_plan.hpp (a progressive session's record buffer,
@@ -110,6 +111,7 @@ static void free_scene(rt_context* c) {
 static void free_context(rt_context* c) {
     free_scene(c);
     c->segs.reset(); c->err.reset(); c->counter.reset(); c->scratch.reset(); c->records.reset(); c->rayskip.reset();
+    c->ballots.reset(); c->tiles.reset();
     if (c->ev_first) (void)hipEventDestroy(c->ev_first);
     if (c->ev_last) (void)hipEventDestroy(c->ev_last);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -393,6 +395,55 @@ extern "C" int rt_path_step_async(rt_context* c, uint64_t n_rays, void* d_origin
     rc = with_precision((flags & RT_FLAG_F32) != 0, [&](auto t) { return launch_step<decltype(t)>(c, a, st); });
     if (rc != RT_OK) return rc;
     return end_launch(c, st, n_rays, 0u);   // samples: the valid rays, counted on the device (kQuerySlot)
+}
+
+// The list checks rt_path_step_list_async and rt_ray_list_compact_async share: the output pair and the ping-pong rule.
+static int check_lists(const std::string& who, const ListArgs& l) {
+    if ((l.list_out != nullptr) != (l.count_out != nullptr))
+        return fail(RT_ERR_INVALID, who + ": d_list_out and d_count_out must be given together (or both NULL)");
+    if (l.list_out && l.list_out == l.list_in)
+        return fail(RT_ERR_INVALID, who + ": d_list_out is d_list_in (ping-pong two lists)");
+    if (l.count_out && l.count_out == l.count_in)
+        return fail(RT_ERR_INVALID, who + ": d_count_out is d_count_in (ping-pong two counts)");
+    return RT_OK;
+}
+
+extern "C" int rt_path_step_list_async(rt_context* c, uint64_t n_rays, const void* d_list_in, const void* d_count_in,
+                                       void* d_origins, void* d_directions, void* d_colour, const void* d_pixel,
+                                       const void* d_sample, uint32_t bounce, uint64_t seed, uint32_t flags,
+                                       void* d_status, void* d_index, void* d_t, void* d_normal, void* d_front,
+                                       void* d_list_out, void* d_count_out, void* stream) {
+    const std::string who = "rt_path_step_list_async";
+    if (!c || !d_origins || !d_directions || !d_pixel || !d_sample)
+        return fail(RT_ERR_INVALID, who + ": NULL argument (ctx, d_origins, d_directions, d_pixel or d_sample)");
+    const ListArgs l{d_list_in, d_count_in, d_list_out, d_count_out, nullptr};
+    int rc = check_lists(who, l);
+    if (rc != RT_OK) return rc;
+    if ((rc = check_step(c, who, n_rays, bounce, flags)) != RT_OK) return rc;
+    if (n_rays == 0) return RT_OK;
+    const StepArgs a{n_rays, d_origins, d_directions, d_colour, d_pixel, d_sample, bounce, seed, flags,
+                     d_status, d_index, d_t, d_normal, d_front};
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = begin_launch(c, st)) != RT_OK) return rc;
+    rc = with_precision((flags & RT_FLAG_F32) != 0, [&](auto t) { return launch_step_list<decltype(t)>(c, a, l, st); });
+    if (rc != RT_OK) return rc;
+    return end_launch(c, st, n_rays, 0u);   // samples: the valid listed rays, counted on the device (kQuerySlot)
+}
+
+extern "C" int rt_ray_list_compact_async(rt_context* c, uint64_t n_rays, const void* d_list_in, const void* d_count_in,
+                                         const void* d_keep, void* d_list_out, void* d_count_out, void* stream) {
+    const std::string who = "rt_ray_list_compact_async";
+    if (!c || !d_keep) return fail(RT_ERR_INVALID, who + ": NULL argument (ctx or d_keep)");
+    if (!d_list_out && !d_count_out) return fail(RT_ERR_INVALID, who + ": no output list (d_list_out and d_count_out are NULL)");
+    const ListArgs l{d_list_in, d_count_in, d_list_out, d_count_out, d_keep};
+    int rc = check_lists(who, l);
+    if (rc != RT_OK) return rc;
+    if (n_rays > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, who + ": too many rays in one call");
+    if (n_rays == 0) return RT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = begin_launch(c, st)) != RT_OK) return rc;
+    if ((rc = launch_compact(c, n_rays, l, st)) != RT_OK) return rc;
+    return end_launch(c, st, n_rays, 0u);   // no samples, no segments: a compaction counts nothing else
 }
 
 extern "C" int rt_render_rays_async(rt_context* c, uint64_t n_pixels, uint32_t spp, uint32_t rays_per_pixel,
@@ -690,7 +741,8 @@ extern "C" int rt_context_collect(rt_context* c, void* stream, rt_stats* out) {
     c->last_kernel_id = c->last_wg_per_cu = 0;
     if (errs[1])
         return fail(RT_ERR_INVALID, "rt_scatter_async / rt_path_step_async: a ray with index >= n_spheres or sample >= 2^20 "
-                                    "(not scattered; the other rays are as they would be without it)");
+                                    "(not scattered; the other rays are as they would be without it); or a ray list with "
+                                    "an entry >= n_rays (skipped) or a count > n_rays (clamped)");
     if (err) return fail(RT_ERR_RANGE, "a pixel channel exceeded 2.0 (Color::to_u8_array would panic, color.rs:55-57)");
     return RT_OK;
 }

@@ -1,13 +1,14 @@
 // rt_launch.hpp — the launches of the C ABI, host only: what the launches of a context share (LaunchContext),
 // the kernel selection and rt_stats.kernel_id, the steps of a launch (context_params, frame_params,
 // ensure_cam_tables, frame_setup, plan_grid) and the launchers (launch_plain, launch_split, launch_window,
-// launch_guides, launch_query, launch_occlusion, launch_scatter, launch_step, launch_rays), between begin_launch and
-// end_launch.
+// launch_guides, launch_query, launch_occlusion, launch_scatter, launch_step, launch_step_list, launch_compact,
+// launch_rays), between begin_launch and end_launch.
 #pragma once
 #include "rt_trace.hpp"
 #include "rt_guides.hpp"
 #include "rt_query.hpp"
 #include "rt_step.hpp"
+#include "rt_list.hpp"
 #include "rt_rays.hpp"
 #include "rt_host.hpp"
 #include "rt_split_plan.hpp"
@@ -35,6 +36,7 @@ struct LaunchContext {
     DeviceBuffer scratch;   // per-wave ray state (grown on demand)
     DeviceBuffer records;   // the sample-parallel path's record buffer (grown on demand)
     DeviceBuffer rayskip;   // rt_render_rays_async: one bit per pixel, set where a ray is invalid (grown on demand)
+    DeviceBuffer ballots, tiles;   // ray lists: a 64-bit survivor word per batch, a sum per tile (grown on demand)
     int n_cu = 0;
     uint64_t samples = 0, pixels = 0;
     hipStream_t last_stream = nullptr;   // stream of the previous render (they share scratch and tables)
@@ -52,6 +54,7 @@ constexpr uint32_t kKernelRaysBit = 1u << 13;     // trace_paths_rays
 constexpr uint32_t kKernelOcclusionBit = 1u << 14;   // occlusion_rays
 constexpr uint32_t kKernelScatterBit = 1u << 16;   // scatter_rays (bit 15: any kernel)
 constexpr uint32_t kKernelStepBit = 1u << 17;      // path_step_rays
+constexpr uint32_t kKernelListBit = 1u << 18;      // with kKernelStepBit: path_step_list; alone: a list compaction
 template <typename T>
 constexpr uint32_t kernel_id(int W, bool root2, int mode, bool camq, bool mega, uint32_t family) {
     return 0x8000u | (sizeof(T) == 8 ? 1u : 0u) | ((uint32_t)W << 1) | (root2 ? kKernelRoot2Bit : 0u) |
@@ -146,6 +149,11 @@ static void (*pick_occlusion(bool root2, bool mega))(OParams<T>) {
 template <typename T>
 static void (*pick_step(bool root2, bool mega))(PsParams<T>) {
     return with_bools([](auto r2, auto mg) { return path_step_rays<T, r2.value, mg.value>; }, root2, mega);
+}
+// The list step's kernel (rt_path_step_list_async): path_step_list<T, ROOT2, MEGA>.
+template <typename T>
+static void (*pick_step_list(bool root2, bool mega))(PlParams<T>) {
+    return with_bools([](auto r2, auto mg) { return path_step_list<T, r2.value, mg.value>; }, root2, mega);
 }
 // The caller-ray kernel (rt_render_rays_async): trace_paths_rays<T, W, ROOT2, MEGA> at the precision's default W.
 template <typename T>
@@ -563,6 +571,114 @@ static int launch_step(LaunchContext* c, const StepArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(sfn, dim3((uint32_t)nblocks), dim3(256), 0, st, pp);
     HIPCHK(hipGetLastError());
     return RT_OK;
+}
+
+// A ray list in and out (rt_path_step_list_async, rt_ray_list_compact_async): any of the four may be NULL as the
+// header says; keep: the compaction call's mask.
+struct ListArgs {
+    const void *list_in, *count_in;
+    void *list_out, *count_out;
+    const void* keep;
+};
+
+// Rays per tile of the compaction's scan: RT_LIST_TILE (64 .. 65536, a power of two; read at every call, any other
+// value ignored), else kListTileDefault.  It changes no result.
+static uint32_t list_tile_env() {
+    const char* e = getenv("RT_LIST_TILE");
+    const long v = e ? atol(e) : 0;
+    return v >= 64 && v <= 65536 && (v & (v - 1)) == 0 ? (uint32_t)v : kListTileDefault;
+}
+
+// The compaction's arguments over a capacity of n rays, its two scratch buffers grown to that capacity.
+static int compact_params(LaunchContext* c, uint64_t n, const ListArgs& l, hipStream_t st, LcParams& p) {
+    const uint32_t tile = list_tile_env();
+    const uint64_t n_batches = (n + 63u) / 64u, n_tiles = (n + tile - 1u) / tile;
+    int rc = ensure_bytes(c->ballots, (size_t)n_batches * sizeof(unsigned long long), st);
+    if (rc != RT_OK) return rc;
+    if ((rc = ensure_bytes(c->tiles, (size_t)n_tiles * sizeof(uint32_t), st)) != RT_OK) return rc;
+    memset(&p, 0, sizeof(p));
+    p.n = (uint32_t)n;
+    p.tile_batches = tile / 64u;
+    p.list_in = (const uint32_t*)l.list_in;
+    p.count_in = (const uint32_t*)l.count_in;
+    p.keep = (const uint8_t*)l.keep;
+    p.ballots = (unsigned long long*)c->ballots.p;
+    p.tiles = (uint32_t*)c->tiles.p;
+    p.list_out = (uint32_t*)l.list_out;
+    p.count_out = (uint32_t*)l.count_out;
+    p.err = (uint32_t*)c->err.p;
+    return RT_OK;
+}
+
+// The three levels of the compaction over the ballots a producer left: the launches are what orders them.  The grids
+// are sized for the capacity (the count stays on the device) and stride; a short list leaves most of them idle.
+static int launch_scan(LaunchContext* c, const LcParams& p, hipStream_t st) {
+    const uint64_t n_batches = ((uint64_t)p.n + 63u) / 64u, n_tiles = (n_batches + p.tile_batches - 1u) / p.tile_batches;
+    const uint64_t cap = (uint64_t)c->n_cu * 8u;   // workgroups
+    hipLaunchKernelGGL(list_tile_sums, dim3((uint32_t)std::min(n_tiles, cap)), dim3(256), 0, st, p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(list_scan_tiles, dim3(1), dim3(kListScanChunk), 0, st, p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(list_scatter, dim3((uint32_t)std::min((n_batches + 3u) / 4u, cap)), dim3(256), 0, st, p);
+    HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// path_step_list over the capacity's batches (launch_step's grid), then the compaction where an output list is asked for.
+template <typename T>
+static int launch_step_list(LaunchContext* c, const StepArgs& a, const ListArgs& l, hipStream_t st) {
+    KParams<T> p;
+    context_params(c, filter_off_env(), p);
+    p.flags = a.flags;
+    p.n_items = (uint32_t)a.n_rays;
+    key_params(a.seed, p);
+    const bool root2 = (a.flags & RT_FLAG_ROOT2) != 0u, mega = p.n_mg > 0;
+    void (*const sfn)(PlParams<T>) = pick_step_list<T>(root2, mega);
+    constexpr int W = kWavesQuery<T>;
+    const uint32_t id = kernel_id<T>(W, root2, kModeV2, false, mega, kKernelStepBit | kKernelListBit);
+    const uint32_t n_batches = (uint32_t)((a.n_rays + 63u) / 64u);   // a wave's work item
+    uint64_t nblocks = 0;
+    int rc = plan_grid(c, (const void*)sfn, W, id, n_batches, 1u, nblocks, p.blk_g);
+    if (rc != RT_OK) return rc;
+    LcParams cp;
+    memset(&cp, 0, sizeof(cp));
+    if (l.list_out && (rc = compact_params(c, a.n_rays, l, st, cp)) != RT_OK) return rc;
+    PlParams<T> lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.s.k = p;
+    lp.s.origins = (T*)a.origins;
+    lp.s.directions = (T*)a.directions;
+    lp.s.colour = (T*)a.colour;
+    lp.s.pixel = (const uint32_t*)a.pixel;
+    lp.s.sample = (const uint32_t*)a.sample;
+    lp.s.bounce = a.bounce;
+    lp.s.status = (uint8_t*)a.status;
+    lp.s.index = (int32_t*)a.index;
+    lp.s.t = (T*)a.t;
+    lp.s.normal = (T*)a.normal;
+    lp.s.front = (uint8_t*)a.front;
+    lp.list_in = (const uint32_t*)l.list_in;
+    lp.count_in = (const uint32_t*)l.count_in;
+    lp.ballots = cp.ballots;   // NULL: no output list
+    hipLaunchKernelGGL(sfn, dim3((uint32_t)nblocks), dim3(256), 0, st, lp);
+    HIPCHK(hipGetLastError());
+    return l.list_out ? launch_scan(c, cp, st) : RT_OK;
+}
+
+// keep_ballots, then the compaction.  The id is the list bit alone unless a kernel with an id of its own ran since the
+// last collect.
+static int launch_compact(LaunchContext* c, uint64_t n, const ListArgs& l, hipStream_t st) {
+    LcParams cp;
+    const int rc = compact_params(c, n, l, st, cp);
+    if (rc != RT_OK) return rc;
+    if (c->last_kernel_id == 0u) {
+        c->last_kernel_id = 0x8000u | kKernelListBit;   // no precision, no occupancy target: F64 0, W 0
+        c->last_wg_per_cu = 0;
+    }
+    const uint64_t n_batches = (n + 63u) / 64u;
+    hipLaunchKernelGGL(keep_ballots, dim3((uint32_t)std::min((n_batches + 3u) / 4u, (uint64_t)c->n_cu * 8u)), dim3(256), 0, st, cp);
+    HIPCHK(hipGetLastError());
+    return launch_scan(c, cp, st);
 }
 
 // What rt_render_rays_async asks for: the rays (R per pixel; origins as a query's) and a render's outputs.

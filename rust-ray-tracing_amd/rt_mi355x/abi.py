@@ -126,6 +126,12 @@ def RT_KERNEL_STEP(kernel_id):
     return (kernel_id >> 17) & 1
 
 
+def RT_KERNEL_LIST(kernel_id):
+    """include/rt_mi355x.h RT_KERNEL_LIST: with RT_KERNEL_STEP the list step ran (rt_path_step_list_async); alone, a
+    list compaction (rt_ray_list_compact_async)."""
+    return (kernel_id >> 18) & 1
+
+
 RT_QUERY_MISS = -1      # include/rt_mi355x.h: rt_query_hits_async's index of a ray that hits nothing
 RT_QUERY_INVALID = -2   # ... and of a ray outside the precondition (not traced)
 RT_OCCLUDED_NO = 0          # include/rt_mi355x.h: rt_query_occluded_async's byte of a ray with nothing before its t_max,
@@ -145,7 +151,8 @@ def kernel_info(kernel_id):
             "split": bool(RT_KERNEL_SPLIT(kernel_id)), "items": bool(RT_KERNEL_ITEMS(kernel_id)),
             "guides": bool(RT_KERNEL_GUIDES(kernel_id)), "query": bool(RT_KERNEL_QUERY(kernel_id)),
             "rays": bool(RT_KERNEL_RAYS(kernel_id)), "occlusion": bool(RT_KERNEL_OCCLUSION(kernel_id)),
-            "scatter": bool(RT_KERNEL_SCATTER(kernel_id)), "step": bool(RT_KERNEL_STEP(kernel_id))}
+            "scatter": bool(RT_KERNEL_SCATTER(kernel_id)), "step": bool(RT_KERNEL_STEP(kernel_id)),
+            "list": bool(RT_KERNEL_LIST(kernel_id))}
 
 
 def kernel_name(kernel_id):
@@ -154,6 +161,10 @@ def kernel_name(kernel_id):
     if k is None:
         return None
     b = lambda v: "true" if v else "false"
+    if k["list"] and k["step"]:   # path_step_list<T,ROOT2,MEGA> (the compaction kernels follow it)
+        return f"path_step_list<{k['T']},{b(k['root2'])},{b(k['mega'])}>"
+    if k["list"]:   # a compaction alone: keep_ballots, then list_tile_sums, list_scan_tiles and list_scatter
+        return "keep_ballots"
     if k["step"]:   # path_step_rays<T,ROOT2,MEGA>
         return f"path_step_rays<{k['T']},{b(k['root2'])},{b(k['mega'])}>"
     if k["scatter"]:   # scatter_rays<T>
@@ -202,15 +213,20 @@ EXPORTED = [
     "rt_progressive_extend_map_async", "rt_progressive_snapshot_map_async", "rt_progressive_counts",
     "rt_progressive_error_async", "rt_progressive_map_plan", "rt_progressive_refine", "rt_progressive_refine_items",
     "rt_render_guides_async", "rt_query_hits_async", "rt_memcpy_h2d", "rt_render_rays_async", "rt_camera_rays",
-    "rt_query_occluded_async", "rt_scatter_async", "rt_path_step_async",
+    "rt_query_occluded_async", "rt_scatter_async", "rt_path_step_async", "rt_path_step_list_async",
+    "rt_ray_list_compact_async",
 ]
+
+LIST_TILE_DEFAULT = 65536   # csrc/rt_list.hpp kListTileDefault: rays per tile of the compaction's scan (RT_LIST_TILE)
+LIST_SCAN_CHUNK = 256       # csrc/rt_list.hpp kListScanChunk: tiles list_scan_tiles scans at once
 
 _lib = None
 
 # The sources the Makefile hashes into rt_version() ("src=<hash>"), in its order (SRC, then HDR).
 KERNEL_SOURCES = ["rt_kernel.hip", "rt_experiments.hpp", "rt_formats.hpp", "rt_common.hpp", "rt_sweep.hpp",
                   "rt_camera.hpp", "rt_finish.hpp", "rt_trace.hpp", "rt_trace_body.hpp", "rt_rays.hpp", "rt_projection.hpp", "rt_layout.hpp", "rt_device.hpp", "rt_split_plan.hpp",
-                  "rt_progressive_plan.hpp", "rt_host.hpp", "rt_launch.hpp", "rt_session.hpp", "rt_guides.hpp", "rt_step.hpp", "rt_query.hpp"]
+                  "rt_progressive_plan.hpp", "rt_host.hpp", "rt_launch.hpp", "rt_session.hpp", "rt_guides.hpp", "rt_step.hpp", "rt_list.hpp",
+                  "rt_query.hpp"]
 SOURCE_FILES = [os.path.join(PKG_DIR, "csrc", f) for f in KERNEL_SOURCES] + \
                [os.path.join(os.path.dirname(PKG_DIR), "include", "rt_mi355x.h")]
 
@@ -268,6 +284,8 @@ def load_library(path=None):
     lib.rt_query_occluded_async.argtypes = [vp, u64, vp, P(f64), vp, vp, f64, u32, vp, vp]
     lib.rt_scatter_async.argtypes = [vp, u64, vp, P(f64), vp, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, vp]
     lib.rt_path_step_async.argtypes = [vp, u64, vp, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, vp, vp, vp]
+    lib.rt_path_step_list_async.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp, u32, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rt_ray_list_compact_async.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp]
     lib.rt_render_rays_async.argtypes = [vp, u64, u32, u32, vp, P(f64), vp, u32, u64, u32, u32, vp, vp, vp]
     lib.rt_camera_rays.argtypes = [P(RtProjection), u32, u32, vp, vp]
     lib.rt_split_plan.argtypes = [u64, u32, u32, P(u32), P(u64)]

@@ -3,7 +3,7 @@ builds once the material stage is public.  path_trace is the reference's Scene::
 (bit for bit a render in mode "vectorized" for a camera's own primary rays); direct_light adds what the reference
 cannot do, a point light with one shadow ray per hit.  Both keep the rays on the device between steps and move one
 status byte and the directions of each step to the host, where the caller's own rules (the sky, retiring, the light)
-run in numpy.
+run in numpy.  path_trace(compact=True) instead steps over ray lists compacted on the device and moves 4 bytes per step.
 """
 import numpy as np
 
@@ -131,7 +131,58 @@ def _loop(renderer, origins, directions, pixel, sample, max_bounces, scene, seed
     return radiance
 
 
-def path_trace(renderer, origins, directions, pixel, sample, max_bounces, scene, seed=None, root2=False, stats=None):
+def _loop_lists(renderer, origins, directions, pixel, sample, max_bounces, scene, seed, root2, stats):
+    """path_trace over ray lists: each step runs over the rays the last one scattered (rt_path_step_list_async) and
+    leaves the next list on the device; the host reads the 4-byte count after each step and the status, the directions
+    and the colour once at the end.  A retired ray is simply no longer listed: its final direction, colour and last
+    status stay where they are."""
+    T = np.dtype(np.float32 if renderer.flags & abi.RT_FLAG_F32 else np.float64)
+    o = np.array(origins, dtype=T, order="C")
+    d = np.array(directions, dtype=T, order="C")
+    n = d.shape[0]
+    pixel = np.arange(n, dtype=np.uint32) if pixel is None else np.ascontiguousarray(pixel, dtype=np.uint32)
+    sample = np.zeros(n, dtype=np.uint32) if sample is None else np.ascontiguousarray(sample, dtype=np.uint32)
+    radiance = np.zeros((n, 3), dtype=T)
+    totals = {"ray_segments": 0, "samples": 0, "kernel_ms": 0.0, "steps": 0, "invalid": 0, "shadow_rays": 0}
+    if stats is not None:
+        stats.update(totals)
+    if n == 0:
+        return radiance
+    renderer._use_scene(_flat(scene))
+    with abi.DeviceScope(renderer.lib, renderer.ctx) as dev:
+        d_o, d_d = DeviceArray(dev, o), DeviceArray(dev, d)
+        d_c = DeviceArray(dev, np.ones((n, 3), dtype=T))
+        d_pix, d_smp = DeviceArray(dev, pixel), DeviceArray(dev, sample)
+        d_st = DeviceArray(dev, np.zeros(n, dtype=np.uint8))   # a ray that is never stepped (max_bounces 0) is not a miss
+        lists = [DeviceArray(dev, shape=(n,), dtype=np.uint32) for _ in range(2)]
+        counts = [DeviceArray(dev, shape=(1,), dtype=np.uint32) for _ in range(2)]
+        live = n
+        for k in range(max_bounces):
+            if live == 0:
+                break
+            src, dst = (k + 1) % 2, k % 2
+            renderer.path_step_list_into(d_o, d_d, d_pix, d_smp, bounce=k, list_in=lists[src] if k else None,
+                                         count_in=counts[src] if k else None, list_out=lists[dst], count_out=counts[dst],
+                                         colour=d_c, status=d_st, seed=seed, root2=root2)
+            st, _ = abi.collect(renderer.lib, renderer.ctx)
+            totals["ray_segments"] += st.ray_segments
+            totals["samples"] += st.samples
+            totals["kernel_ms"] += st.kernel_ms
+            totals["steps"] += 1
+            live = int(counts[dst].get()[0])
+        status, dn, colour = d_st.get(), d_d.get(), d_c.get()
+    if max_bounces > 0:
+        missed = status == abi.RT_STEP_MISSED
+        totals["invalid"] = int(np.count_nonzero(status == abi.RT_STEP_INVALID))
+        # a miss multiplies by the sky of the ray's own final direction; a ray still alive at the end is 0
+        radiance[missed] += colour[missed] * sky(dn[missed, 1])
+    if stats is not None:
+        stats.update(totals)
+    return radiance
+
+
+def path_trace(renderer, origins, directions, pixel, sample, max_bounces, scene, seed=None, root2=False, stats=None,
+               compact=False):
     """Scene::trace_vectorized as a loop over rt_path_step_async: the colour starts at 1; for k in 0..max_bounces a
     hit scatters, a miss multiplies by sky(d.y) of the ray's own final direction and retires (its direction is zeroed,
     so later steps do not trace it); a ray still alive at the end is 0.  origins, directions: (n, 3); pixel, sample:
@@ -139,7 +190,13 @@ def path_trace(renderer, origins, directions, pixel, sample, max_bounces, scene,
     Returns the per-ray radiance (n, 3) in the renderer's precision.  Fed a camera's primary rays (pixel = row W + col,
     sample = s) and reduced with reduce_samples, this is render()'s linear image in mode "vectorized", bit for bit, as
     long as no ray leaves the query's |d|^2 range (stats["invalid"] counts those).
-    stats: a dict that receives ray_segments, samples, kernel_ms, steps and invalid summed over the steps."""
+    stats: a dict that receives ray_segments, samples, kernel_ms, steps and invalid summed over the steps.
+    compact: step over ray lists compacted on the device (GpuRenderer.path_step_list_into): each step runs over the
+    rays the last one scattered, the host reads one 4-byte count per step and the status, directions and colour once
+    at the end.  The same values bit for bit, and the same ray_segments, samples, steps and invalid, as long as
+    stats["invalid"] is 0: a ray whose final status is invalid is 0 here, where the plain loop retires it as a miss."""
+    if compact:
+        return _loop_lists(renderer, origins, directions, pixel, sample, max_bounces, scene, seed, root2, stats)
     return _loop(renderer, origins, directions, pixel, sample, max_bounces, scene, seed, root2, stats, None)
 
 

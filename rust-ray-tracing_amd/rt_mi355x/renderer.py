@@ -21,6 +21,7 @@ from . import abi
 from .checks import (ADAPTIVE_PLANS, GUIDE_CHANNELS, GUIDE_NAMES, QUERY_NAMES, QUERY_OUTPUTS, Guides,  # noqa: F401
                      _device_array, _query_shape, check_adaptive, check_guides, check_query, check_query_into,
                      check_render_rays, check_render_rays_into, check_schedule, check_stream, split_argument)
+from .list_checks import check_compact_list_into, check_path_step_list_into
 from .occlusion_checks import check_occluded, check_occluded_into, check_scene_set  # noqa: F401
 from .step_checks import (STEP_NAMES, STEP_OUTPUTS, _step_shape, check_path_step, check_path_step_into,  # noqa: F401
                           check_scatter, check_scatter_into, check_seed, check_step_names)
@@ -574,6 +575,36 @@ class GpuRenderer(Renderer):
         check_stream(stream)
         check_step_scene(self._scene_flat, "path_step_into")
         abi.check(self.lib, self._launch_step(n, d_org, d_dir, d_col, d_pix, d_smp, bounce, seed, flags, ptrs, stream))
+        return n
+
+    def path_step_list_into(self, origins, directions, pixel, sample, *, bounce, list_in=None, count_in=None,
+                            list_out=None, count_out=None, colour=None, status=None, index=None, t=None, normal=None,
+                            front=None, seed=None, root2=False, stream=None):
+        """rt_path_step_list_async on device arrays in place: path_step_into over the rays a list names, leaving the
+        next list on the device (include/rt_mi355x.h has the definition).  The ray arrays are path_step_into's, indexed
+        by ray id; list_in (n,) uint32 and count_in (1,) uint32 name the rays (None: the identity list, count n);
+        list_out (n,) uint32 and count_out (1,) uint32, given together, receive the rays that scattered, in list
+        order.  Nothing is written at a ray that is not listed.  Returns the number of rays n (the capacity)."""
+        flags = self._query_flags(root2)
+        n, d_org, d_dir, d_col, d_pix, d_smp, ptrs, bounce, lists = check_path_step_list_into(
+            flags, self.device, origins, directions, pixel, sample, colour,
+            dict(status=status, index=index, t=t, normal=normal, front=front), bounce, list_in, count_in, list_out, count_out)
+        seed = check_seed(seed)
+        check_stream(stream)
+        check_step_scene(self._scene_flat, "path_step_list_into")
+        d_li, d_ci, d_lo, d_co = lists
+        abi.check(self.lib, self.lib.rt_path_step_list_async(
+            self.ctx, n, d_li, d_ci, d_org, d_dir, d_col, d_pix, d_smp, bounce, self.seed if seed is None else seed, flags,
+            *[ptrs.get(name) for name in STEP_NAMES], d_lo, d_co, stream))
+        return n
+
+    def compact_list_into(self, keep, list_out, count_out, *, list_in=None, count_in=None, stream=None):
+        """rt_ray_list_compact_async on device arrays: list_out receives, in list order, the entries r of list_in
+        (None: 0 .. n - 1; count_in None: all n) with keep[r] != 0, and count_out how many.  keep: (n,) uint8 by ray id
+        (a step's status array builds a list of the scattered and invalid rays).  Returns n."""
+        n, d_keep, (d_li, d_ci, d_lo, d_co) = check_compact_list_into(self.device, keep, list_out, count_out, list_in, count_in)
+        check_stream(stream)
+        abi.check(self.lib, self.lib.rt_ray_list_compact_async(self.ctx, n, d_li, d_ci, d_keep, d_lo, d_co, stream))
         return n
 
     def render_rays(self, max_bounces, spp, origins, directions, scene, seed=None, pixel_base=0, root2=False,
